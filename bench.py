@@ -28,6 +28,11 @@ the host time per step and changes no GPU time).
 A storm-step is one hourly output interval of one live storm.
 Inputs (fields) are resident in HBM before the timed region; candidates are drawn
 on the device inside it.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (`roofline`, `cpu_baseline` null, `gpu_active_s` null when
+no timing events ran).  --full adds what takes runs of its own after the timed region: five isolated batches for the per-kernel
+roofline, the integrator's pass statistics and the CPU baseline (unless --no-cpu-baseline).
+--dump-outputs DIR writes what the last timed step computed (rank 0's batch) as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -72,7 +77,12 @@ def main():
     ap.add_argument('--dup-seed', type=int, default=1, help=argparse.SUPPRESS)
     ap.add_argument('--dup-select', type=int, default=1, help=argparse.SUPPRESS)
     ap.add_argument('--basin', default='GL')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also run the isolated batches of the per-kernel roofline, the pass statistics and '
+                         'the CPU baseline (off: the line carries roofline / cpu_baseline null)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed (rank 0) as DIR/<name>.npy, float64 / float32, < 64 MB')
     ap.add_argument('--order', choices=('cells', 'candidate'), default='cells',
                     help='cells: the dense batch in locality order (2-degree genesis cells, tcr_cell_order_dev; DESIGN.md §9); '
                          'candidate: candidate order')
@@ -250,6 +260,12 @@ def main():
     torch.cuda.synchronize(); D.barrier()
     dt = time.perf_counter() - t0
     dt = D.max_over_ranks(dt, dev)
+    if args.dump_outputs and rank == 0:
+        k_last = w_eff + args.steps - 1
+        # (the track sample's fraction follows from the arguments alone: ~1 024 rows with --rows all, ~16 384 storms otherwise)
+        per_rank = args.storms / world if strong else args.storms
+        dump_outputs(args.dump_outputs, pipes[k_last % n_str], D.round_block(k_last, C, rank, world), args.rows == 'all',
+                     track_frac=min(1.0, (1024 if args.rows == 'all' else 16384) / max(per_rank, 1)))
     rows_gathered, rows_clipped = (gather.rows_gathered, gather.rows_clipped) if gather is not None else (None, None)
 
     def sum_timings():
@@ -276,12 +292,12 @@ def main():
     # SIMD time of the integrator chains as they ran INSIDE the timed region (the last batch of every stream: wave residency
     # summed from the waves' own wall-clock stamps): under load the waves of several batches share the CUs' address paths,
     # so this is what a chain costs the pipeline; `integrate_passes` below is the same for an isolated batch
-    pipe_passes = [e.pass_stats() for e in engs]
+    pipe_passes = [e.pass_stats() for e in engs] if args.full else []
     # The same kernels once more, one launch at a time on one stream (after the timed region, not
     # part of `value`): with several streams the event-bracketed duration of a launch includes the
     # time it shared the GPU with other batches, so the per-kernel roofline is quoted both ways.
     iso = None
-    if True:
+    if args.full:
         acc_keep = acc.clone()
         for e in engs:
             e.timing_enable(True)
@@ -314,98 +330,103 @@ def main():
     assert int(n_overflow) == 0, '%d storms overflowed their step record (tcr_params.max_rk_steps)' % int(n_overflow)
     value = steps_total / dt
 
-    # ---- roofline of the dominant kernel (k_integrate): algorithmic bytes per launch
-    # (704 B x RHS evaluations of that launch) over its HIP-event duration
-    # (events recorded on the launch stream by the library).  The per-sample share of the
-    # algorithmic bytes (520 B x output samples) is k_emit's and is reported next to it.
-    static_tag = '%g/%s' % (args.static_res, args.static_store)
     launches = ms['calls']
     have_events = launches > 0
-    if have_events:
-        k_ms = ms['integrate_ms'] / launches
-        e_ms = ms['post_ms'] / launches
-        int_bytes = BYTES_PER_RHS * nfev_total / (launches * world)
     # HIP-event time of every kernel of the timed region, summed over launches and streams (overlapping
     # streams make this exceed the wall time; it shows the GPU was busy even when SMI sampling misses a 50 ms region).
-    # Graph replays record no events: the figure is then the isolated batches' kernel time x the timed steps.
+    # Graph replays record no events: the figure is then the isolated batches' kernel time x the timed steps (--full; a plain
+    # run without events has no kernel time to report).
     if have_events:
         gpu_active_s = (ms['fourier_ms'] + ms['integrate_ms'] + ms['post_ms']) * 1e-3
-    else:
+    elif iso is not None:
         gpu_active_s = (iso['fourier_ms'] + iso['integrate_ms'] + iso['post_ms']) / iso['calls'] * args.steps * 1e-3
-    traffic, traffic_src = (args.traffic, 'command line') if args.traffic is not None else measured_traffic('k_integrate', args.storms if world == 1 else B, args.rows, args.dtype, args.order, static_tag, args.shape)
-    # Exclusive duration: the same launch, one batch at a time on one stream right after the timed region
-    # (3 batches).  With several streams the event-bracketed duration of a launch in the timed region
-    # includes time it shared the GPU with other batches (it can exceed ms_per_step), so that figure is
-    # kept under `pipelined_events`, not at the top level.
-    ik, ie = iso['integrate_ms'] / iso['calls'], iso['post_ms'] / iso['calls']
-    ib = BYTES_PER_RHS * iso_counts[1] / iso['calls']
-    eb = BYTES_PER_SAMPLE * (iso_counts[5] if args.rows == 'tc' else iso_counts[2]) / iso['calls']
-    achieved = ib / (ik * 1e-3) / 1e9
-    e_traffic, e_src = measured_traffic('k_emit', args.storms if world == 1 else B, args.rows, args.dtype, args.order, static_tag, args.shape)
-    roof = dict(bound='hbm', kernel='k_integrate', achieved=achieved, peak=HBM_PEAK_GBS, unit='GB/s',
-                frac=achieved / HBM_PEAK_GBS, traffic=traffic, traffic_source=traffic_src,
-                note='a launch = the chain of k_integrate passes of one batch (tail compaction); achieved = %d B x RHS ' % BYTES_PER_RHS +
-                     'evaluations of the batch / exclusive HIP-event duration of the chain (one batch at a time on one '
-                     'stream, after the timed region: median of five); profiles/ lists k_integrate once per pass',
-                algorithmic_bytes_per_launch=ib, launch_ms=ik,
-                kernel_ms=dict(fourier=iso['fourier_ms'] / iso['calls'], integrate=ik, post=ie),
-                pipelined_events=(dict(note='event-bracketed durations inside the timed region, %d streams overlapping' % n_str,
-                                       launch_ms=k_ms, achieved=int_bytes / (k_ms * 1e-3) / 1e9,
-                                       frac=int_bytes / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                       kernel_ms=dict(fourier=ms['fourier_ms'] / launches, integrate=k_ms, post=e_ms))
-                                  if have_events else None),
-                sustained=dict(note='algorithmic bytes of all k_integrate launches / wall time of the timed region',
-                               achieved=BYTES_PER_RHS * nfev_total / world / dt / 1e9,
-                               frac=BYTES_PER_RHS * nfev_total / world / dt / 1e9 / HBM_PEAK_GBS),
-                emit=dict(kernel='k_screen + k_dense + k_emit + k_flags' if args.rows == 'tc' else 'k_dense + k_emit + k_flags',
-                          note='%d B x samples actually emitted (%s) / exclusive duration of the post-processing'
-                               % (BYTES_PER_SAMPLE, 'storms that pass accept test 1' if args.rows == 'tc' else 'every storm'),
-                          achieved=eb / (ie * 1e-3) / 1e9, frac=eb / (ie * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                          algorithmic_bytes_per_launch=eb, launch_ms=ie, traffic=e_traffic, traffic_source=e_src))
-    # k_integrate runs as a chain of passes (tail compaction); occupancy of the last isolated batch:
-    # wave_ms = summed wave residency, i.e. SIMD time (one integrator wave owns a SIMD's registers)
-    wc = sum(p['wave_cycles'] for p in iso_passes)
-    simds = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
-    st_ms = sum(p['wave_ms'] for p in iso_passes) / simds
-    roof['integrate_passes'] = dict(
-        passes=len(iso_passes), lane_utilisation=sum(p['lane_cycles'] for p in iso_passes) / max(1, 64 * wc),
-        wave_ms=sum(p['wave_ms'] for p in iso_passes), simds=simds, simd_time_ms=st_ms,
-        shader_mhz_pass0=iso_passes[0]['shader_mhz'] if iso_passes else None,
-        # the same algorithmic bytes over the SIMD time the chain occupies (what it costs a pipelined run)
-        achieved_over_simd_time=ib / (st_ms * 1e-3) / 1e9, frac_over_simd_time=ib / (st_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
+    else:
+        gpu_active_s = None
+    roof = None
+    if args.full:
+        # ---- roofline of the dominant kernel (k_integrate): algorithmic bytes per launch
+        # (704 B x RHS evaluations of that launch) over its HIP-event duration
+        # (events recorded on the launch stream by the library).  The per-sample share of the
+        # algorithmic bytes (520 B x output samples) is k_emit's and is reported next to it.
+        static_tag = '%g/%s' % (args.static_res, args.static_store)
+        if have_events:
+            k_ms = ms['integrate_ms'] / launches
+            e_ms = ms['post_ms'] / launches
+            int_bytes = BYTES_PER_RHS * nfev_total / (launches * world)
+        traffic, traffic_src = (args.traffic, 'command line') if args.traffic is not None else measured_traffic('k_integrate', args.storms if world == 1 else B, args.rows, args.dtype, args.order, static_tag, args.shape)
+        # Exclusive duration: the same launch, one batch at a time on one stream right after the timed region
+        # (3 batches).  With several streams the event-bracketed duration of a launch in the timed region
+        # includes time it shared the GPU with other batches (it can exceed ms_per_step), so that figure is
+        # kept under `pipelined_events`, not at the top level.
+        ik, ie = iso['integrate_ms'] / iso['calls'], iso['post_ms'] / iso['calls']
+        ib = BYTES_PER_RHS * iso_counts[1] / iso['calls']
+        eb = BYTES_PER_SAMPLE * (iso_counts[5] if args.rows == 'tc' else iso_counts[2]) / iso['calls']
+        achieved = ib / (ik * 1e-3) / 1e9
+        e_traffic, e_src = measured_traffic('k_emit', args.storms if world == 1 else B, args.rows, args.dtype, args.order, static_tag, args.shape)
+        roof = dict(bound='hbm', kernel='k_integrate', achieved=achieved, peak=HBM_PEAK_GBS, unit='GB/s',
+                    frac=achieved / HBM_PEAK_GBS, traffic=traffic, traffic_source=traffic_src,
+                    note='a launch = the chain of k_integrate passes of one batch (tail compaction); achieved = %d B x RHS ' % BYTES_PER_RHS +
+                         'evaluations of the batch / exclusive HIP-event duration of the chain (one batch at a time on one '
+                         'stream, after the timed region: median of five); profiles/ lists k_integrate once per pass',
+                    algorithmic_bytes_per_launch=ib, launch_ms=ik,
+                    kernel_ms=dict(fourier=iso['fourier_ms'] / iso['calls'], integrate=ik, post=ie),
+                    pipelined_events=(dict(note='event-bracketed durations inside the timed region, %d streams overlapping' % n_str,
+                                           launch_ms=k_ms, achieved=int_bytes / (k_ms * 1e-3) / 1e9,
+                                           frac=int_bytes / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                           kernel_ms=dict(fourier=ms['fourier_ms'] / launches, integrate=k_ms, post=e_ms))
+                                      if have_events else None),
+                    sustained=dict(note='algorithmic bytes of all k_integrate launches / wall time of the timed region',
+                                   achieved=BYTES_PER_RHS * nfev_total / world / dt / 1e9,
+                                   frac=BYTES_PER_RHS * nfev_total / world / dt / 1e9 / HBM_PEAK_GBS),
+                    emit=dict(kernel='k_screen + k_dense + k_emit + k_flags' if args.rows == 'tc' else 'k_dense + k_emit + k_flags',
+                              note='%d B x samples actually emitted (%s) / exclusive duration of the post-processing'
+                                   % (BYTES_PER_SAMPLE, 'storms that pass accept test 1' if args.rows == 'tc' else 'every storm'),
+                              achieved=eb / (ie * 1e-3) / 1e9, frac=eb / (ie * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                              algorithmic_bytes_per_launch=eb, launch_ms=ie, traffic=e_traffic, traffic_source=e_src))
+        # k_integrate runs as a chain of passes (tail compaction); occupancy of the last isolated batch:
+        # wave_ms = summed wave residency, i.e. SIMD time (one integrator wave owns a SIMD's registers)
+        wc = sum(p['wave_cycles'] for p in iso_passes)
+        simds = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
+        st_ms = sum(p['wave_ms'] for p in iso_passes) / simds
+        roof['integrate_passes'] = dict(
+            passes=len(iso_passes), lane_utilisation=sum(p['lane_cycles'] for p in iso_passes) / max(1, 64 * wc),
+            wave_ms=sum(p['wave_ms'] for p in iso_passes), simds=simds, simd_time_ms=st_ms,
+            shader_mhz_pass0=iso_passes[0]['shader_mhz'] if iso_passes else None,
+            # the same algorithmic bytes over the SIMD time the chain occupies (what it costs a pipelined run)
+            achieved_over_simd_time=ib / (st_ms * 1e-3) / 1e9, frac_over_simd_time=ib / (st_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
 
-    # The whole step against the memory system: fabric-side bytes of ALL kernels of a step (rocprofv3 --pmc, corrected with the
-    # factor calibrated on this access pattern) over the measured time per step.  Reducing the integrator's SIMD time (lane
-    # utilisation 0.73 -> 0.91) does not move the step, removing the forcing table's traffic does:
-    # the step sits at ~0.9 of what scattered 128-byte line fills reach on this chip (tools/calibrate_fetch.hip: 4.26 TB/s).
-    # BASELINE.md section 3's figure for the whole step, from the one driver-timed number: algorithmic bytes of everything the
-    # timed region did — 704 B x RHS evaluations + 520 B x samples emitted — over its wall time, against the 8 TB/s peak
-    alg_gbs = (BYTES_PER_RHS * nfev_total + BYTES_PER_SAMPLE * emitted_total) / world / dt / 1e9
-    roof['step_algorithmic'] = dict(achieved=alg_gbs, unit='GB/s', peak=HBM_PEAK_GBS, frac=alg_gbs / HBM_PEAK_GBS,
-                                    note='(%d B x RHS evaluations + %d B x emitted samples) of the timed region / its wall time, per GPU'
-                                         % (BYTES_PER_RHS, BYTES_PER_SAMPLE))
-    step_bytes, step_src = measured_traffic('*', args.storms, args.rows, args.dtype, args.order, static_tag, args.shape) if world == 1 else (None, None)
-    if step_bytes and world == 1:
-        gbs = step_bytes / (dt / args.steps) / 1e9
-        ceil_gbs, ceil_src = scattered_line_fill_ceiling()
-        roof['whole_step'] = dict(traffic=step_bytes, traffic_source=step_src, achieved=gbs, unit='GB/s', peak=HBM_PEAK_GBS,
-                                  frac=gbs / HBM_PEAK_GBS, achievable=HBM_ACHIEVABLE_GBS, frac_of_achievable=gbs / HBM_ACHIEVABLE_GBS,
-                                  scattered_line_fill_ceiling=ceil_gbs, scattered_line_fill_ceiling_source=ceil_src,
-                                  frac_of_scattered_line_fill_ceiling=(gbs / ceil_gbs) if ceil_gbs else None,
-                                  note='fabric-side traffic (L2 misses incl. Infinity-Cache hits) of every kernel of a step / ms_per_step; '
-                                       'achievable = MI355X_MICROARCH.md (~6.3 TB/s of the 8 TB/s peak); the line-fill ceiling is this '
-                                       "project's own calibration run (1 GiB of 128-B lines gathered once each, 7 x 16 B per lane)")
-    simds_ = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
-    pw = [sum(p['wave_ms'] for p in ps) for ps in pipe_passes if ps]
-    if pw:
-        roof['integrate_passes_pipelined'] = dict(
-            simd_time_ms=sum(pw) / len(pw) / simds_, batches=len(pw),
-            lane_utilisation=sum(p['lane_cycles'] for ps in pipe_passes for p in ps) / max(1, 64 * sum(p['wave_cycles'] for ps in pipe_passes for p in ps)),
-            note='wave residency of the k_integrate passes of the last timed batch of every stream / SIMDs')
+        # The whole step against the memory system: fabric-side bytes of ALL kernels of a step (rocprofv3 --pmc, corrected with the
+        # factor calibrated on this access pattern) over the measured time per step.  Reducing the integrator's SIMD time (lane
+        # utilisation 0.73 -> 0.91) does not move the step, removing the forcing table's traffic does:
+        # the step sits at ~0.9 of what scattered 128-byte line fills reach on this chip (tools/calibrate_fetch.hip: 4.26 TB/s).
+        # BASELINE.md section 3's figure for the whole step, from the one driver-timed number: algorithmic bytes of everything the
+        # timed region did — 704 B x RHS evaluations + 520 B x samples emitted — over its wall time, against the 8 TB/s peak
+        alg_gbs = (BYTES_PER_RHS * nfev_total + BYTES_PER_SAMPLE * emitted_total) / world / dt / 1e9
+        roof['step_algorithmic'] = dict(achieved=alg_gbs, unit='GB/s', peak=HBM_PEAK_GBS, frac=alg_gbs / HBM_PEAK_GBS,
+                                        note='(%d B x RHS evaluations + %d B x emitted samples) of the timed region / its wall time, per GPU'
+                                             % (BYTES_PER_RHS, BYTES_PER_SAMPLE))
+        step_bytes, step_src = measured_traffic('*', args.storms, args.rows, args.dtype, args.order, static_tag, args.shape) if world == 1 else (None, None)
+        if step_bytes and world == 1:
+            gbs = step_bytes / (dt / args.steps) / 1e9
+            ceil_gbs, ceil_src = scattered_line_fill_ceiling()
+            roof['whole_step'] = dict(traffic=step_bytes, traffic_source=step_src, achieved=gbs, unit='GB/s', peak=HBM_PEAK_GBS,
+                                      frac=gbs / HBM_PEAK_GBS, achievable=HBM_ACHIEVABLE_GBS, frac_of_achievable=gbs / HBM_ACHIEVABLE_GBS,
+                                      scattered_line_fill_ceiling=ceil_gbs, scattered_line_fill_ceiling_source=ceil_src,
+                                      frac_of_scattered_line_fill_ceiling=(gbs / ceil_gbs) if ceil_gbs else None,
+                                      note='fabric-side traffic (L2 misses incl. Infinity-Cache hits) of every kernel of a step / ms_per_step; '
+                                           'achievable = MI355X_MICROARCH.md (~6.3 TB/s of the 8 TB/s peak); the line-fill ceiling is this '
+                                           "project's own calibration run (1 GiB of 128-B lines gathered once each, 7 x 16 B per lane)")
+        simds_ = 4 * torch.cuda.get_device_properties(dev).multi_processor_count
+        pw = [sum(p['wave_ms'] for p in ps) for ps in pipe_passes if ps]
+        if pw:
+            roof['integrate_passes_pipelined'] = dict(
+                simd_time_ms=sum(pw) / len(pw) / simds_, batches=len(pw),
+                lane_utilisation=sum(p['lane_cycles'] for ps in pipe_passes for p in ps) / max(1, 64 * sum(p['wave_cycles'] for ps in pipe_passes for p in ps)),
+                note='wave residency of the k_integrate passes of the last timed batch of every stream / SIMDs')
     out = None
     backend = D.backend_name()
     # (the sample of the CPU baseline: the first storms of rank 0's last batch)
-    sample = cpu_sample(pipe, B) if (rank == 0 and not args.no_cpu_baseline) else None
+    sample = cpu_sample(pipe, B) if (rank == 0 and args.full and not args.no_cpu_baseline) else None
     if D.collective():
         D.barrier()
         torch.distributed.destroy_process_group()
@@ -471,6 +492,60 @@ def self_launch(n):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n), '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.call(cmd)
+
+
+def candidate_hash(cand):
+    """splitmix64 of global candidate indices -> floats in [0, 1): whether a storm belongs to the dumped track sample depends on
+    its candidate index alone, never on what a build computed for it or for any other storm."""
+    import numpy as np
+    z = cand.astype(np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(11)).astype(np.float64) / float(1 << 53)
+
+
+def dump_outputs(out_dir, pipe, cand0, rows_all, track_frac, max_storms=1 << 18, max_rows=1536, seed=20240601):
+    """--dump-outputs: what the step last run on `pipe` computed, as out_dir/<name>.npy, in global candidate order (so that two
+    builds compare output for output whatever order their batches take).  Per storm (at most `max_storms`, a fixed seeded
+    sample beyond that): the seeds that passed (cand_index, lon0, lat0, v0, m0, h_bl, month) and the integrator's results
+    (n_valid, status, flags, nfev, n_accept, n_reject).  Tracks: the storms whose candidate_hash is below `track_frac` (a sample
+    fixed by the inputs) and that have rows (every storm with --rows all, else those that pass accept test 1), at most
+    `max_rows` of them (the lowest hashes), named by rows_cand_index with their lengths in rows_n_valid: lon / lat / v / m / vmax
+    [rows, n_steps] and envw [rows, n_steps, 4], 0 beyond each track's end instead of the planes' NaN padding, so that a storm
+    two builds disagree on changes its own row only.  Integers are written as float64, planes in the path's dtype: ~34 MB at
+    100 000 storms, at most ~50 MB."""
+    import numpy as np
+    import torch
+    from tropical_cyclone_risk_amd import _lib
+    os.makedirs(out_dir, exist_ok=True)
+    n = min(int(pipe.n_done), int(pipe.n_passed.item()))
+    rng = np.random.default_rng(seed)
+    cand = pipe.cand_idx[:n].cpu().numpy().astype(np.int64) + int(cand0)
+    order = np.argsort(cand, kind='stable')
+    if n > max_storms:
+        order = order[np.sort(rng.choice(n, max_storms, replace=False))]
+    t, s = pipe.tracks, pipe.storms
+    per = lambda a: a[:n].cpu().numpy()[order]
+    arrays = dict(cand_index=cand[order], lon0=per(s['lon0']), lat0=per(s['lat0']), v0=per(s['v0']), m0=per(s['m0']),
+                  h_bl=per(s['h_bl']), month=per(s['slot']) + 1)
+    for k in ('n_valid', 'status', 'flags', 'nfev', 'n_accept', 'n_reject'):
+        arrays[k] = per(t[k])
+    has_rows = np.ones(len(order), bool) if rows_all else (arrays['flags'] & _lib.FLAG_IS_TC) != 0
+    h = candidate_hash(arrays['cand_index'])
+    rows = np.flatnonzero(has_rows & (h < track_frac))
+    if len(rows) > max_rows:
+        rows = np.sort(rows[np.argsort(h[rows], kind='stable')[:max_rows]])
+    arrays['rows_cand_index'] = arrays['cand_index'][rows]
+    arrays['rows_n_valid'] = arrays['n_valid'][rows]
+    idx = torch.from_numpy(order[rows]).to(pipe.dev)
+    nv = torch.from_numpy(arrays['rows_n_valid'].astype(np.int64)).to(pipe.dev)
+    for k in ('lon', 'lat', 'v', 'm', 'vmax', 'envw'):
+        a = t[k].index_select(0, idx)
+        past = torch.arange(a.shape[1], device=pipe.dev)[None, :] >= nv[:, None]      # beyond each track's last sample
+        arrays[k] = a.masked_fill(past if a.dim() == 2 else past[:, :, None], 0.0).cpu().numpy()
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a if a.dtype.kind == 'f' else a.astype(np.float64))
 
 
 def scattered_line_fill_ceiling():

@@ -42,7 +42,7 @@ def test_forced_collectives_switch_is_off_by_default():
 
 def _bench(extra_env, *flags):
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--scaling', 'strong', '--storms', '12000', '--streams', '4', '--steps', '6',
-           '--warmup', '2'] + list(flags)
+           '--warmup', '2', '--full'] + list(flags)
     r = subprocess.run(cmd, env=_env(**extra_env), cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
@@ -94,10 +94,99 @@ def test_run_py_through_rccl_on_one_rank(built_lib, tmp_path, shard_years):
     assert out['plain']['lon_trks'].shape == (72, 361)
 
 
-def _bench_cmd(n, *flags, timeout=1500):
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(built_lib, tmp_path):
+    """A plain run (no --full) times the steps and prints the line without the roofline's isolated batches or the CPU baseline;
+    --dump-outputs writes the last timed step's outputs in candidate order, under 64 MB, and two runs with the same arguments
+    write the same arrays bit for bit."""
+    dumps = []
+    for tag in ('a', 'b'):
+        d = tmp_path / tag
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--storms', '12000', '--streams', '4', '--steps', '3',
+               '--warmup', '1', '--dump-outputs', str(d)]
+        r = subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0 and line['higher_is_better'] is True
+        assert line['unit'] == 'storm-steps/s' and line['dtype'] == 'f64'
+        assert line['roofline'] is None and line['cpu_baseline'] is None
+        files = sorted(os.listdir(d))
+        assert {'cand_index.npy', 'n_valid.npy', 'flags.npy', 'rows_cand_index.npy', 'lon.npy', 'vmax.npy', 'envw.npy'} <= set(files)
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) < 64 << 20
+        arrays = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        cand, rows = arrays['cand_index.npy'], arrays['rows_cand_index.npy']
+        assert abs(len(cand) - 12000) < 400 and np.all(np.diff(cand) > 0)
+        # the storms of the LAST timed step: its candidate block (strong scaling, one rank: step k draws [k C, (k + 1) C))
+        k_last, C = line['config']['warmup_effective'] + line['steps'] - 1, line['config']['candidates_per_round']
+        assert cand.min() >= k_last * C and cand.max() < (k_last + 1) * C
+        # 12 000 storms: the track sample takes every storm with rows, i.e. every storm that passes accept test 1
+        is_tc = (arrays['flags.npy'].astype(np.int64) & 1) != 0
+        assert np.array_equal(rows, cand[is_tc]) and 0 < len(rows) <= 1536
+        j = np.searchsorted(cand, rows)
+        nv = arrays['rows_n_valid.npy']
+        assert np.array_equal(nv, arrays['n_valid.npy'][j]) and nv.min() >= 1
+        assert arrays['lon.npy'].shape == (len(rows), 361) and arrays['envw.npy'].shape == (len(rows), 361, 4)
+        # each track belongs to the storm it is listed under: it starts at that storm's genesis point, 0 beyond its end
+        assert np.abs(arrays['lon.npy'][:, 0] - arrays['lon0.npy'][j]).max() <= 1e-9
+        assert np.abs(arrays['lat.npy'][:, 0] - arrays['lat0.npy'][j]).max() <= 1e-9
+        past = np.arange(361)[None, :] >= nv[:, None]
+        assert not arrays['vmax.npy'][past].any() and not arrays['envw.npy'][past].any()
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f], equal_nan=True), f
+
+
+def test_dumped_track_sample_depends_on_candidates_only():
+    """bench.dump_outputs on a host-side stand-in for a pipeline: the track sample is chosen by the candidate index, so when one
+    storm's results change (its is_tc flag, its length) only that storm's row changes; every other row stays as it was, bit
+    for bit, and the planes keep their fixed [rows, n_steps] shape, 0 beyond each track's end."""
+    import tempfile
+    import types
+    import torch
+    import bench
+    n, ns = 30000, 361
+    g = torch.Generator().manual_seed(7)
+    f = lambda *shape: torch.rand(*shape, dtype=torch.float64, generator=g)
+    i32 = lambda lo, hi: torch.randint(lo, hi, (n,), dtype=torch.int32, generator=g)
+    perm = torch.randperm(2 * n, generator=g)[:n].to(torch.int32)
+    seeds = dict(lon0=f(n), lat0=f(n), v0=f(n), m0=f(n), h_bl=f(n), slot=i32(0, 12))
+    planes = dict(lon=f(n, ns), lat=f(n, ns), v=f(n, ns), m=f(n, ns), vmax=f(n, ns), envw=f(n, ns, 4))
+    flags, n_valid, st = i32(0, 4), i32(1, ns + 1), i32(0, 5)
+    frac = 0.05
+    in_sample = bench.candidate_hash(perm.numpy().astype(np.int64) + 1000) < frac
+    tc = (flags.numpy() & 1) != 0
+    k0, k1 = int(np.flatnonzero(in_sample & ~tc)[0]), int(np.flatnonzero(in_sample & tc & (n_valid.numpy() > 10))[0])
+    out = []
+    for change in (False, True):
+        fl, nv = flags.clone(), n_valid.clone()
+        if change:           # one storm of the sample gains accept test 1, another one's track gets shorter
+            fl[k0] |= 1
+            nv[k1] = int(nv[k1]) // 2
+        pipe = types.SimpleNamespace(dev=torch.device('cpu'), n_done=n, n_passed=torch.tensor([n]), cand_idx=perm, storms=seeds,
+                                     tracks=dict(planes, n_valid=nv, flags=fl, status=st, nfev=st, n_accept=st, n_reject=st))
+        d = tempfile.mkdtemp()
+        bench.dump_outputs(d, pipe, 1000, False, track_frac=frac)
+        out.append({k: np.load(os.path.join(d, k + '.npy')) for k in ('rows_cand_index', 'rows_n_valid', 'lon', 'envw')})
+    a, b = out
+    for o in out:
+        k = len(o['rows_cand_index'])
+        assert o['lon'].shape == (k, ns) and o['envw'].shape == (k, ns, 4) and np.isfinite(o['lon']).all()
+        assert not o['lon'][np.arange(ns)[None, :] >= o['rows_n_valid'][:, None]].any()
+    common, ia, ib = np.intersect1d(a['rows_cand_index'], b['rows_cand_index'], return_indices=True)
+    assert set(b['rows_cand_index']) - set(a['rows_cand_index']) == {int(perm[k0]) + 1000} and len(common) == len(a['rows_cand_index'])
+    assert len(common) > 300
+    same = [np.array_equal(a['lon'][x], b['lon'][y]) and np.array_equal(a['envw'][x], b['envw'][y]) for x, y in zip(ia, ib)]
+    assert [common[i] for i in range(len(common)) if not same[i]] == [int(perm[k1]) + 1000]
+
+
+def _bench_cmd(n, *flags, timeout=1500, full=True):
     """`python bench.py --gpus N ...` exactly as the driver types it for N = 1 — no launcher: bench.py starts its N ranks itself
-    (self_launch).  TCR_DIST_BACKEND=gloo lets the ranks share this box's one GPU."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '4', '--warmup', '1', '--storms', '12000'] + list(flags)
+    (self_launch).  TCR_DIST_BACKEND=gloo lets the ranks share this box's one GPU.  full: with --full (roofline, CPU baseline)."""
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '4', '--warmup', '1', '--storms', '12000'] + \
+        (['--full'] if full else []) + list(flags)
     r = subprocess.run(cmd, env=_env(TCR_DIST_BACKEND='gloo'), cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -131,6 +220,14 @@ def test_launcherless_bench_at_2_4_8_ranks(built_lib):
             assert cpu is not None and cpu['value'] and cpu['value'] > 0 and cpu['cores'] >= 1 and cpu['kind'] == 'port'
         else:
             assert cpu is None
+    # ... and the plain N = 2 command, without --full: one line, the same totals, no roofline / CPU baseline
+    d = _bench_cmd(2, full=False)
+    c = d['config']
+    assert d['n_gpus'] == 2 and d['steps'] == 4 and d['value'] > 0 and d['ms_per_step'] > 0
+    assert d['roofline'] is None and d['cpu_baseline'] is None
+    assert c['allgather_rows'] == c['accepted_total'] > 0 and c['allgather_rows_clipped'] == 0
+    for k in ('storm_steps_total', 'accepted_total', 'storms_per_step'):
+        assert c[k] == c1[k], (2, k, c[k], c1[k])
 
 
 @pytest.mark.gpu

@@ -323,7 +323,7 @@ def test_bench_multi_rank_path(built_lib, tmp_path):
             cmd = [sys.executable] + (['-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(world), '--master-addr',
                                        '127.0.0.1', '--master-port', '29531'] if world > 1 else []) + \
                   [os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', '4', '--warmup', '1', '--storms', str(storms),
-                   '--streams', '2', '--no-cpu-baseline', '--scaling', mode] + (['--graph', 'on'] if mode == 'strong' else [])
+                   '--streams', '2', '--full', '--no-cpu-baseline', '--scaling', mode] + (['--graph', 'on'] if mode == 'strong' else [])
             r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
             assert r.returncode == 0, r.stderr[-2000:]
             out[mode, world] = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/r05
 rm -rf "$OUT"; mkdir -p "$OUT"
-B="timeout 900 python bench.py"
+B="timeout 900 python bench.py --full"
 # 1. the bench line: the driver's flags, the script's own defaults, and the static-field shape of rounds 1-4 for continuity
 $B --steps 20 --warmup 5 2>"$OUT/bench.err" | tail -1 > "$OUT/bench_driver_flags.json"
 $B --no-cpu-baseline 2>>"$OUT/bench.err" | tail -1 > "$OUT/bench.json"
@@ -24,7 +24,7 @@ done
 # 4. per-kernel timing, one stream and the default twelve
 for s in 1 12; do
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats$s" -o s -- \
-      python bench.py --steps 10 --warmup 2 --streams $s --no-cpu-baseline > /dev/null 2>&1
+      python bench.py --full --steps 10 --warmup 2 --streams $s --no-cpu-baseline > /dev/null 2>&1
   cp "$(find "$OUT/stats$s" -name '*kernel_stats.csv' | head -1)" "$OUT/kernel_stats_streams$s.csv"
   rm -rf "$OUT/stats$s"
 done
@@ -33,7 +33,7 @@ i=0
 for C in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"; do
   i=$((i+1))
   timeout 600 rocprofv3 --kernel-trace --output-format csv --pmc $C -d "$OUT/pmc$i" -o p -- \
-      python bench.py --steps 3 --warmup 1 --streams 1 --no-cpu-baseline > /dev/null 2>&1
+      python bench.py --full --steps 3 --warmup 1 --streams 1 --no-cpu-baseline > /dev/null 2>&1
 done
 python tools/summarize_pmc.py "$OUT" tc 0.125/auto > "$OUT/pmc_hbm.json"
 rm -rf "$OUT"/pmc[123]

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=gpurun_out/r06c
 rm -rf "$OUT"; mkdir -p "$OUT"
-B="timeout 600 python bench.py"
+B="timeout 600 python bench.py --full"
 # 1. the bench line: the driver's flags, the script's own defaults
 $B --steps 20 --warmup 5 2>"$OUT/bench.err" | tail -1 > "$OUT/bench_driver_flags.json"
 $B --no-cpu-baseline 2>>"$OUT/bench.err" | tail -1 > "$OUT/bench.json"
@@ -23,7 +23,7 @@ $B --steps 20 --warmup 5 --no-cpu-baseline --shape gfdl 2>>"$OUT/bench.err" | ta
 # 4. per-kernel timing, one stream and the default twelve; the 12-stream trace also feeds the timeline
 for s in 1 12; do
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats$s" -o s -- \
-      python bench.py --steps 10 --warmup 2 --streams $s --no-cpu-baseline > /dev/null 2>&1
+      python bench.py --full --steps 10 --warmup 2 --streams $s --no-cpu-baseline > /dev/null 2>&1
   cp "$(find "$OUT/stats$s" -name '*kernel_stats.csv' | head -1)" "$OUT/kernel_stats_streams$s.csv"
   [ $s = 12 ] && python tools/timeline.py "$(find "$OUT/stats$s" -name '*kernel_trace.csv' | head -1)" 6 5 > "$OUT/timeline_streams12.txt" 2>&1
   rm -rf "$OUT/stats$s"
@@ -33,7 +33,7 @@ i=0
 for C in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"; do
   i=$((i+1))
   timeout 300 rocprofv3 --kernel-trace --output-format csv --pmc $C -d "$OUT/pmc$i" -o p -- \
-      python bench.py --steps 3 --warmup 1 --streams 1 --no-cpu-baseline > /dev/null 2>&1
+      python bench.py --full --steps 3 --warmup 1 --streams 1 --no-cpu-baseline > /dev/null 2>&1
 done
 python tools/summarize_pmc.py "$OUT" tc 0.125/auto > "$OUT/pmc_hbm.json"
 rm -rf "$OUT"/pmc[123]

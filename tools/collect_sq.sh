@@ -31,11 +31,11 @@ i=0
 for C in "${PASSES[@]}"; do
   i=$((i+1))
   timeout 150 rocprofv3 --kernel-trace --output-format csv --pmc $C -d "$OUT/s${s}_p$i" -o p -- \
-      python bench.py --steps 3 --warmup 1 --streams $s --no-cpu-baseline > "$OUT/s${s}_p$i.log" 2>&1
+      python bench.py --full --steps 3 --warmup 1 --streams $s --no-cpu-baseline > "$OUT/s${s}_p$i.log" 2>&1
   echo "pass $i ($C) rc $?" >> "$OUT/passes.txt"
 done
 for s in 1 12; do
-  timeout 300 python bench.py --steps 20 --warmup 5 --streams $s --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/bench_streams$s.json"
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --streams $s --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/bench_streams$s.json"
 done
 python tools/summarize_sq.py "$OUT" > "$OUT/../sq_summary_$TAG.json"
 find "$OUT" -name '*.csv' -size +2M -delete

@@ -11,10 +11,10 @@ OUT=gpurun_out/$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 for RES in 0.25 0.125; do
   for rep in 1 2; do
-    timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --static-res $RES --static-store $STORE 2>>"$OUT/bench.err" | tail -1 > "$OUT/bench_res${RES}_$rep.json"
+    timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --static-res $RES --static-store $STORE 2>>"$OUT/bench.err" | tail -1 > "$OUT/bench_res${RES}_$rep.json"
   done
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats$RES" -o s -- \
-      python bench.py --steps 10 --warmup 2 --streams 1 --no-cpu-baseline --static-res $RES --static-store $STORE > /dev/null 2>&1
+      python bench.py --full --steps 10 --warmup 2 --streams 1 --no-cpu-baseline --static-res $RES --static-store $STORE > /dev/null 2>&1
   cp "$(find "$OUT/stats$RES" -name '*kernel_stats.csv' | head -1)" "$OUT/kernel_stats_streams1_res$RES.csv"
   rm -rf "$OUT/stats$RES"
   i=0
@@ -22,7 +22,7 @@ for RES in 0.25 0.125; do
   for C in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"; do
     i=$((i+1))
     timeout 600 rocprofv3 --kernel-trace --output-format csv --pmc $C -d "$OUT/pmc_res$RES/pmc$i" -o p -- \
-        python bench.py --steps 3 --warmup 1 --streams 1 --no-cpu-baseline --static-res $RES --static-store $STORE > /dev/null 2>&1
+        python bench.py --full --steps 3 --warmup 1 --streams 1 --no-cpu-baseline --static-res $RES --static-store $STORE > /dev/null 2>&1
   done
   python tools/summarize_pmc.py "$OUT/pmc_res$RES" tc > "$OUT/pmc_hbm_res$RES.json"
   rm -rf "$OUT/pmc_res$RES"

@@ -24,10 +24,10 @@ for v in /tmp/product.so build_variants/*.so; do
   cp "$v" $LIB
   echo "== $n (rep $rep)"
   timeout 300 python tools/pass_stats.py 2>&1 | grep -E "^integrate|^total"
-  timeout 300 python bench.py --steps 20 --warmup 5 --streams 1 --no-cpu-baseline 2>/dev/null | line "streams1 "
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | line "streams12"
-  timeout 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | line "streams12/40"
-  timeout 300 python bench.py --no-cpu-baseline --scaling weak --storms 12500 --streams 16 --steps 240 --warmup 32 2>/dev/null | line "12500x16 "
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --streams 1 --no-cpu-baseline 2>/dev/null | line "streams1 "
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | line "streams12"
+  timeout 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | line "streams12/40"
+  timeout 300 python bench.py --full --no-cpu-baseline --scaling weak --storms 12500 --streams 16 --steps 240 --warmup 32 2>/dev/null | line "12500x16 "
 done
 done 2>&1 | tee $OUT/ab.txt
 cp /tmp/product.so $LIB

@@ -58,7 +58,7 @@ tot_raw = sum(e.get('hbm_bytes_per_batch_raw', 0.0) for e in res.values())
 rows = sys.argv[2] if len(sys.argv) > 2 else 'tc'
 static = sys.argv[3] if len(sys.argv) > 3 else '0.125/auto'       # --static-res / --static-store of the profiled runs
 command = ('rocprofv3 --kernel-trace --output-format csv --pmc <FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum> -- '
-           'python bench.py --steps 3 --warmup 1 --streams 1 --rows %s --no-cpu-baseline (three separate runs)' % rows)
+           'python bench.py --full --steps 3 --warmup 1 --streams 1 --rows %s --no-cpu-baseline (three separate runs)' % rows)
 meta = dict(workload='GL, 100000 storms per batch; the first batch of each run pads whole plane rows (pad_state = -1)',
             units='FETCH_SIZE / WRITE_SIZE in KiB as rocprofv3 reports them; *_per_batch = summed over the dispatches of a bench step',
             fetch_factor=FETCH_FACTOR, fetch_factor_source=FETCH_SRC,

@@ -62,7 +62,7 @@ for s in (1, 12):
         res['bench_streams_%d' % s] = e
     except Exception as ex:
         res['bench_streams_%d' % s] = 'unavailable: %s' % ex
-meta = dict(command='rocprofv3 --kernel-trace --output-format csv --pmc <pass> -- python bench.py --steps 3 --warmup 1 --streams S --no-cpu-baseline '
+meta = dict(command='rocprofv3 --kernel-trace --output-format csv --pmc <pass> -- python bench.py --full --steps 3 --warmup 1 --streams S --no-cpu-baseline '
                     '(one run per pass, passes listed in tools/collect_sq.sh; rocprofv3 serialises dispatches while counters are collected)',
             units='counter sums per bench step (all dispatches of that kernel in one step, all SEs / XCDs summed as rocprofv3 reports them); '
                   'SQ cycle counters are quad-cycles',

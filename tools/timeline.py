@@ -1,7 +1,7 @@
 """GPU timeline of a bench run from a rocprofv3 --kernel-trace csv: how busy was the chip during the timed steps?
     python tools/timeline.py gpurun_out/r03e/t4/t_kernel_trace.csv [n_steps] [skip_last]
 Per queue the dispatches are serial; across queues they overlap.  Reports, over the window that holds N k_flags dispatches
-(one per step) ending skip_last dispatches before the last one (bench.py ends with five isolated batches on one stream: skip 5): wall time per step, union-busy fraction, mean number of kernels in flight, the integrator's
+(one per step) ending skip_last dispatches before the last one (bench.py --full ends with five isolated batches on one stream: skip 5): wall time per step, union-busy fraction, mean number of kernels in flight, the integrator's
 SIMD demand (sum over its dispatches of min(workgroups, SIMDs) x duration / (SIMDs x wall)), and per-kernel time shares."""
 import collections
 import csv

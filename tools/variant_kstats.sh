@@ -9,7 +9,7 @@ for v in /tmp/product.so build_variants/*.so; do
   echo "== $v"
   cp "$v" $LIB
   rm -rf /tmp/prof
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o gs -- python bench.py --steps 10 --warmup 2 --streams 1 --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o gs -- python bench.py --full --steps 10 --warmup 2 --streams 1 --no-cpu-baseline > /dev/null 2>&1
   python tools/print_kernel_stats.py /tmp/prof | grep -E "${1:-.}" | head -${2:-6}
 done
 cp /tmp/product.so $LIB
