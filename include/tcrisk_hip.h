@@ -504,6 +504,32 @@ int tcr_allreduce_sum_i64_dev(tcr_comm *comm, int64_t *buf_dev, int64_t n, void 
 int tcr_concat_rows_dev(tcr_ctx *ctx, int32_t n_blocks, const double *gathered_dev, const int64_t *counts_dev, int64_t cap, int64_t row_stride,
                         double *out_dev, int64_t out_cap, int64_t *n_out_dev, void *stream);
 
+/* ---- site hazard: near-site intensity and exceedance counts ------------------------------------------------------- */
+/* replaces: the analysis of notebooks/sample_analysis.ipynb on a track file, for n_site sites at once:
+ *   max[site][storm]          = nanmax of vmax over the live samples (lon, lat not NaN) within radius_km of the site, by the
+ *                               notebook's haversine (r_earth = 6378 km; NaN when there are none)
+ *   counts[site][g][b] (int32) = #storms s in [group_off[g], group_off[g + 1]) with max[site][s] >= thresholds[b]
+ * lon / lat / vmax are the track file's lon_trks / lat_trks / vmax_trks, [n_trk][row_stride] with n_t samples used per row; sites
+ * and tracks may use either longitude convention.  0 < radius_km <= 5000, 1 <= n_bin <= 64, thresholds finite and strictly
+ * ascending, group_off non-decreasing from 0 to n_trk.  Results are bit-identical from run to run and do not depend on the
+ * order of the sites; storms and sites far apart are skipped in blocks, so sites given in a spatially coherent order (runs of 64
+ * neighbours) run fastest.  site_max (optional, NULL: not written) is [n_site][n_trk].
+ * _dev: lon / lat / vmax, site_lon / site_lat, counts and site_max are device memory, asynchronous on `stream`;
+ * group_off and thresholds are host memory in both entry points.  Workspaces belong to the context (grown on demand): calls on
+ * one context must be ordered (one stream, or the previous call finished). */
+typedef struct {
+    int64_t n_trk, n_t, row_stride;
+    const double *lon, *lat, *vmax;
+    int32_t n_group;
+    const int64_t *group_off;              /* host, [n_group + 1] */
+} tcr_hazard_tracks;
+int tcr_hazard_dev(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, int64_t n_site, const double *site_lon, const double *site_lat,
+                   double radius_km, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_max, void *stream);
+int tcr_hazard_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, int64_t n_site, const double *site_lon, const double *site_lat,
+                    double radius_km, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_max);
+/* (site, sample) distance tests the last tcr_hazard_* call of this context evaluated after culling; waits for that call */
+int tcr_hazard_pairs(tcr_ctx *ctx, int64_t *pairs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,6 +215,13 @@ struct tcr_ctx {
     std::vector<hipEvent_t> st_pool;
     std::vector<int> st_id;
     size_t st_used = 0;
+    // site hazard (tcr_hazard.hip): samples, caps, live counts, partial counts, chunk table; the pinned staging of the chunk table
+    void *d_hz[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t hz_cap[5] = {0, 0, 0, 0, 0};
+    int64_t *hz_h = nullptr;
+    size_t hz_h_cap = 0;
+    hipEvent_t hz_ev = nullptr, hz_done = nullptr;  // chunk table uploaded / last call done
+    unsigned long long *hz_pairs = nullptr;         // pairs the last call evaluated (inside d_hz[4])
 };
 
 namespace {
@@ -1076,6 +1083,10 @@ int tcr_ctx_destroy(tcr_ctx *ctx)
     for (auto &ev : ctx->st_pool) if (ev) (void)hipEventDestroy(ev);
     for (auto &g : ctx->graphs) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); }
     (void)hipFree(ctx->d_round_key);
+    for (void *p : ctx->d_hz) (void)hipFree(p);
+    if (ctx->hz_h) (void)hipHostFree(ctx->hz_h);
+    if (ctx->hz_ev) (void)hipEventDestroy(ctx->hz_ev);
+    if (ctx->hz_done) (void)hipEventDestroy(ctx->hz_done);
     for (int i = 0; i < 2; ++i) { if (ctx->h_stage[i]) (void)hipHostFree(ctx->h_stage[i]); if (ctx->h_stage_ev[i]) (void)hipEventDestroy(ctx->h_stage_ev[i]); }
     (void)hipFree(ctx->d_hist_partial); (void)hipFree(ctx->d_cell); (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_tc_idx); (void)hipFree(ctx->d_tc_count); (void)hipFree(ctx->d_queue); (void)hipFree(ctx->d_sidx); (void)hipFree(ctx->d_park[0]); (void)hipFree(ctx->d_park[1]); (void)hipFree(ctx->d_sc_table); (void)hipFree(ctx->d_pf); (void)hipFree(ctx->d_screen_skip); (void)hipFree(ctx->d_und_list); (void)hipFree(ctx->d_und_count); (void)hipFree(ctx->d_tab);
     (void)hipStreamDestroy(ctx->stream);
@@ -2305,3 +2316,4 @@ int tcr_round_graph_stats(tcr_ctx *ctx, int64_t *n_graphs, int64_t *n_replays)
 }  // extern "C"
 
 #include "tcr_comm.hip"                  // multi-GPU exchange (RCCL, loaded at run time)
+#include "tcr_hazard.hip"                // site wind hazard (near-site intensity, exceedance counts)
