@@ -530,6 +530,37 @@ int tcr_hazard_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, int64_t n_sit
 /* (site, sample) distance tests the last tcr_hazard_* call of this context evaluated after culling; waits for that call */
 int tcr_hazard_pairs(tcr_ctx *ctx, int64_t *pairs);
 
+/* ---- landfall: sea -> land steps of the model's land decision ---------------------------------------------------- */
+/* replaces: nothing in the reference's code (its README's landfall return periods); the land decision is the one the model
+ * switches its physics on, f_land.ev(lon, lat) == 1 on the bilinear interpolant of intensity/data/land.nc, taken on the nodes:
+ *   land node       land >= 1 (NaN: water)
+ *   sample's cell   by comparisons only: i = the last lon node <= x (0 below the grid: clamped as FITPACK does); node i + 1 has
+ *                   a nonzero weight iff it exists and lon_i < x; the same for lat.  A grid is periodic when
+ *                   lon[nlon-1] - lon[0] + (lon[1] - lon[0]) == 360 exactly: x is reduced first, t = fmod(x - lon0, 360),
+ *                   t += 360 when t < 0, x = lon0 + t (lon0 when that rounds to lon0 + 360), and the last cell wraps to node 0.
+ *   over land       every node with a nonzero bilinear weight is a land node (no arithmetic: the `== 1` flicker does not enter)
+ *   event           a live sample k (lon, lat not NaN) over land whose previous live sample p is not; per event: k, lon[k],
+ *                   lat[k], v_landfall = vmax[p], v_inland = vmax[k] (NaN kept).  A storm that starts over land has no event there.
+ * Hourly samples can step over a land strip narrower than an hour's motion: such a crossing is not an event.
+ * tcr_land_upload: nlon, nlat >= 2, lon / lat finite and strictly ascending, land [nlat][nlon] (host memory); replaces the
+ * context's grid (no tcr_landfall_* call of the context may be in flight).  tcr_land_info: the uploaded grid's sizes and periodic flag.
+ * tcr_landfall_*: the tracks' group fields are ignored.  n_landfall [n_trk] (int32) counts every event; the first
+ * min(n_landfall, max_events) go to ev_k (int32), ev_lon, ev_lat, ev_v, ev_v_inland [n_trk][max_events] in order, the rest of a
+ * row is ev_k = -1 and NaN.  max_events >= 0 (0: counts only; the event planes may be NULL).  flags (optional, NULL: not
+ * written) [n_trk][n_t] uint8: 0 water, 1 land, 2 not live.  Results are copies of inputs and integers: bit-identical from run to
+ * run.  _dev: tracks and outputs are device memory, asynchronous on `stream`. */
+typedef struct {
+    int64_t nlon, nlat;
+    const double *lon, *lat;               /* host, [nlon], [nlat] */
+    const double *land;                    /* host, [nlat][nlon] */
+} tcr_land_grid;
+int tcr_land_upload(tcr_ctx *ctx, const tcr_land_grid *grid);
+int tcr_land_info(tcr_ctx *ctx, int64_t *nlon, int64_t *nlat, int32_t *periodic);
+int tcr_landfall_dev(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, int32_t max_events, int32_t *n_landfall, int32_t *ev_k,
+                     double *ev_lon, double *ev_lat, double *ev_v, double *ev_v_inland, uint8_t *flags, void *stream);
+int tcr_landfall_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, int32_t max_events, int32_t *n_landfall, int32_t *ev_k,
+                      double *ev_lon, double *ev_lat, double *ev_v, double *ev_v_inland, uint8_t *flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,8 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_static_store', 'tcr_static_info', 'tcr_tune_set', 'tcr_tune_get', 'tcr_slot_upload', 'tcr_stage_timing',
            'tcr_probe_math_host', 'tcr_comm_unique_id', 'tcr_comm_create', 'tcr_comm_destroy', 'tcr_comm_rank', 'tcr_comm_world', 'tcr_allgather_dev',
            'tcr_allgather_rows_dev', 'tcr_allgather_counts_dev', 'tcr_allreduce_sum_i64_dev', 'tcr_concat_rows_dev',
-           'tcr_hazard_dev', 'tcr_hazard_host', 'tcr_hazard_pairs')
+           'tcr_hazard_dev', 'tcr_hazard_host', 'tcr_hazard_pairs', 'tcr_land_upload', 'tcr_land_info', 'tcr_landfall_dev',
+           'tcr_landfall_host')
 TCR_COMM_ID_BYTES = 128
 
 
@@ -103,6 +104,11 @@ class HazardTracks(C.Structure):
     """tcr_hazard_tracks: the track planes of tcr_hazard_* and the storm groups (group_off is host memory)."""
     _fields_ = [('n_trk', C.c_int64), ('n_t', C.c_int64), ('row_stride', C.c_int64), ('lon', C.c_void_p), ('lat', C.c_void_p),
                 ('vmax', C.c_void_p), ('n_group', C.c_int32), ('group_off', C.POINTER(C.c_int64))]
+
+
+class LandGrid(C.Structure):
+    """tcr_land_grid: the land grid of tcr_land_upload (host memory)."""
+    _fields_ = [('nlon', C.c_int64), ('nlat', C.c_int64), ('lon', C.c_void_p), ('lat', C.c_void_p), ('land', C.c_void_p)]
 
 
 class TcrError(RuntimeError):
@@ -228,6 +234,10 @@ def lib():
     L.tcr_hazard_host.argtypes = [C.c_void_p, C.POINTER(HazardTracks), C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, DP,
                                   C.c_void_p, C.c_void_p]
     L.tcr_hazard_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.tcr_land_upload.argtypes = [C.c_void_p, C.POINTER(LandGrid)]
+    L.tcr_land_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    L.tcr_landfall_dev.argtypes = [C.c_void_p, C.POINTER(HazardTracks), C.c_int32] + [C.c_void_p] * 8
+    L.tcr_landfall_host.argtypes = [C.c_void_p, C.POINTER(HazardTracks), C.c_int32] + [C.c_void_p] * 7
     if L.tcr_abi_version() != TCR_ABI_VERSION:
         raise TcrError('libtcrisk_hip.so ABI version %d != binding version %d'
                        % (L.tcr_abi_version(), TCR_ABI_VERSION))
