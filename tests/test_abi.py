@@ -168,3 +168,26 @@ def test_product_library_reads_the_environment_once():
     for f in ('tcr_kernels.hip', 'tcr_seed.hip', 'tcr_compact.hip', 'tcr_prep.hip', 'tcr_thermo.hip', 'tcr_device.h'):
         assert 'getenv' not in open(os.path.join(B.CSRC, f)).read(), f
     assert 'TCR_EXPERIMENTS' not in ' '.join(B.FLAGS)
+
+
+def test_build_knobs_are_the_documented_ones():
+    """The product library is the sources' defaults (no -D in build.FLAGS), and the only build-time forks of the kernels are
+    the arithmetic policy (tcr_device.h), the launch-shape defaults and the experiment hooks: a timing experiment's #if
+    does not stay behind in the product source once its result is recorded."""
+    import glob
+    from tropical_cyclone_risk_amd import build as B
+    allowed = {'TCR_FUSE', 'TCR_FUSE_RK', 'TCR_FUSE_RHS', 'TCR_FAST_DIV', 'TCR_FAST_SQRT', 'TCR_FAST_POW', 'TCR_FAST_COS',
+               'TCR_SHARE_COS',
+               'TCR_FS_THREADS', 'TCR_FS_PER_THREAD', 'TCR_FS_MFMA', 'TCR_FS_MFMA_TILES', 'TCR_FS_MFMA_WPS', 'TCR_FS_MFMA_WAVES',
+               'TCR_INT_WPS', 'TCR_INT_WPS_F32', 'TCR_POST_THREADS', 'TCR_EMIT_GRID_CAP', 'TCR_EMIT_WPS', 'TCR_SHADOW_WPS',
+               'TCR_EXPERIMENTS'}
+    files = glob.glob(os.path.join(B.CSRC, '*.hip')) + glob.glob(os.path.join(B.CSRC, '*.h')) + [os.path.join(ROOT, 'include', 'tcrisk_hip.h')]
+    found = {}
+    for f in files:
+        for line in open(f):
+            if re.match(r'\s*#\s*(if|ifdef|ifndef|elif)\b', line):
+                for knob in re.findall(r'\bTCR_[A-Z0-9_]+', line):
+                    found.setdefault(knob, os.path.basename(f))
+    assert len(files) > 10 and 'TCR_FUSE' in found
+    assert {k: f for k, f in found.items() if k not in allowed} == {}
+    assert not [f for f in B.FLAGS if f.startswith('-D')], B.FLAGS

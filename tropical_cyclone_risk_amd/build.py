@@ -19,11 +19,8 @@ SOURCES = ['tcr_abi.hip', 'tcr_kernels.hip', 'tcr_seed.hip', 'tcr_compact.hip', 
            os.path.join('..', '..', 'include', 'tcrisk_hip.h')]
 # -disable-machine-licm: the kernels here are register-bound loops around libm-heavy bodies; hoisting the bodies' constant
 # materialisations out of the loops costs k_emit 40 VGPRs + spills (0.36 instead of 0.15 ms) and k_integrate 70 AGPRs.
-# -DTCR_K_KERNARG: k_integrate reads its ~100 evaluation constants with scalar loads from the kernel arguments instead of from the
-# workgroup's LDS copy behind an opaque offset (-DTCR_OPAQUE_K, rounds 2-5: needed while LLVM hoisted them into registers and the
-# kernel spilled; without machine LICM neither form spills).  Round 6, same box: chain -3 %, 100 000-storm step -1.5 %, bit-identical.
-FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-DTCR_K_KERNARG', '-mllvm', '-disable-machine-licm',
-         '-fPIC', '-shared']
+# No -D: the product library is the sources' defaults.
+FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-mllvm', '-disable-machine-licm', '-fPIC', '-shared']
 
 
 def hipcc():
@@ -33,22 +30,23 @@ def hipcc():
     raise RuntimeError('hipcc not found; libtcrisk_hip.so cannot be built (no CPU fallback exists)')
 
 
-def stale():
-    if not os.path.exists(OUT):
+def stale(out=OUT):
+    if not os.path.exists(out):
         return True
-    t = os.path.getmtime(OUT)
+    t = os.path.getmtime(out)
     return os.path.getmtime(os.path.abspath(__file__)) > t or any(os.path.getmtime(os.path.join(CSRC, s)) > t for s in SOURCES)
 
 
-def build(force=False, verbose=False):
-    if not (force or stale()):
-        return OUT
-    extra = os.environ.get('TCR_HIPCC_FLAGS', '').split()      # tuning experiments, e.g. -DTCR_EMIT_WPS=4
-    cmd = [hipcc()] + FLAGS + extra + ['-o', OUT, os.path.join(CSRC, 'tcr_abi.hip')]
+def build(force=False, verbose=False, flags=(), out=OUT):
+    """flags: extra hipcc arguments for a tuning variant (tools/build_variant.py), e.g. -DTCR_EMIT_WPS=4; the product takes none.
+    stale() does not look at flags, so a variant must go to an `out` of its own."""
+    if not (force or stale(out)):
+        return out
+    cmd = [hipcc()] + FLAGS + list(flags) + ['-o', out, os.path.join(CSRC, 'tcr_abi.hip')]
     if verbose:
         print(' '.join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)
-    return OUT
+    return out
 
 
 if __name__ == '__main__':

@@ -824,12 +824,12 @@ struct CornerCacheT {
 
 template <typename R> __device__ __forceinline__ void cache_reset(CornerCacheT<R> &C) { C.wi = C.wj = -1; }
 
-// One evaluation of fun for the sequential integrator, cut at the two points where its data dependencies allow the
-// next stage point's memory round trip to start early (k_integrate):
+// One evaluation of fun for the sequential integrator, cut where its data dependencies split it (k_integrate runs the
+// three parts in order, once per evaluation slot):
 //   issue      cell searches and every gather of the point (lon, lat, t) — needs nothing but the point;
 //   track      raw env winds and d lon/dt, d lat/dt — all the *next* stage point depends on; also reduces the thermo /
 //              static corners to their bilinear values, so the load registers are free for the next issue;
-//   intensity  dv/dt, dm/dt — runs in the shadow of the next point's gathers.
+//   intensity  dv/dt, dm/dt (rhs_intensity).
 // The operations and their order per value are those of rhs_eval; only independent work is reordered.
 template <typename R, bool AFFINE, int SM>
 struct RhsPipeT {
@@ -847,62 +847,13 @@ struct RhsPipeT {
         tx = wx; ty = wy;
         if (!RD(K.tw_same)) { tx = locate_t<R, AFFINE>(K.tx, lon); ty = locate_t<R, AFFINE>(K.ty, lat); }      // wave-uniform
         fb = fs_bracket(K, t);
-#ifdef TCR_ABLATE_UNIFORM_ADDR
-        // timing experiment only (values are wrong): every lane gathers at lane 0's cells — one cache line per load
-        // instruction instead of up to 64 — which separates the per-lane cost of a gather from its per-line cost
-        wx.i = __builtin_amdgcn_readfirstlane(wx.i); wy.i = __builtin_amdgcn_readfirstlane(wy.i);
-        tx.i = __builtin_amdgcn_readfirstlane(tx.i); ty.i = __builtin_amdgcn_readfirstlane(ty.i);
-        fb.lo = __builtin_amdgcn_readfirstlane(fb.lo);
-        {
-            auto first64 = [](unsigned long long v) {
-                const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-                return ((unsigned long long)hi << 32) | lo;
-            };
-            fs = reinterpret_cast<const R *>(first64((unsigned long long)fs));
-            wind = reinterpret_cast<const R *>(first64((unsigned long long)wind));
-            thermo = reinterpret_cast<const R *>(first64((unsigned long long)thermo));
-            lon = (R)__longlong_as_double((long long)first64((unsigned long long)__double_as_longlong((double)lon)));
-            lat = (R)__longlong_as_double((long long)first64((unsigned long long)__double_as_longlong((double)lat)));
-        }
-#endif
-#if defined(TCR_ABLATE_FS_READ) || defined(TCR_ABLATE_ALL_READS)
-        // timing experiment of DESIGN.md §9 only (values are wrong): what the integrator would gain if the forcing-table
-        // read cost nothing.  The bracket arithmetic stays; the gather becomes a cheap per-lane constant.
-        for (int k = 0; k < 4 / FsPairT<R>::L; ++k) for (int q = 0; q < FsPairT<R>::L; ++q) { fp.a[k][q] = (R)(1e-3 * fb.lo); fp.b[k][q] = (R)(1e-3 * fb.lo); }
-#else
         fs_gather<R>(fs, fb, fp);
-#endif
-#ifdef TCR_ABLATE_ALL_READS
-        // timing experiment only (values are not physical): every gather of the evaluation replaced by per-lane constants
-        {
-            const R eps = (R)(1e-6 * wx.i);
-            for (int f = 0; f < 14; ++f) {
-                const R c = ((f == 4 || f == 6 || f == 9 || f == 13) ? R(10) : (f < 4 ? R(3) : R(0.1))) + eps;
-                C.CW.c00[f / Wd::W][f % Wd::W] = c; C.CW.c01[f / Wd::W][f % Wd::W] = c;
-                C.CW.c10[f / Wd::W][f % Wd::W] = c; C.CW.c11[f / Wd::W][f % Wd::W] = c;
-            }
-            const R tv[4] = {R(60), R(0.5), R(50), R(0.05)};
-            for (int f = 0; f < 4; ++f) {
-                const R c = tv[f] + eps;
-                CT.c00[f / Wd::T][f % Wd::T] = c; CT.c01[f / Wd::T][f % Wd::T] = c;
-                CT.c10[f / Wd::T][f % Wd::T] = c; CT.c11[f / Wd::T][f % Wd::T] = c;
-            }
-            SL.hx = locate_t<R, AFFINE>(K.hx, lon); SL.hy = locate_t<R, AFFINE>(K.hy, lat);
-            const R sv[2] = {R(0), R(-3000)};
-            for (int f = 0; f < 2; ++f) {
-                const R c = sv[f] + eps;
-                SL.CH.c00[f / Wd::H][f % Wd::H] = c; SL.CH.c01[f / Wd::H][f % Wd::H] = c;
-                SL.CH.c10[f / Wd::H][f % Wd::H] = c; SL.CH.c11[f / Wd::H][f % Wd::H] = c;
-            }
-        }
-#else
         if (wx.i != C.wi || wy.i != C.wj) {
             gather<R, 14, kWindStride, Wd::W>(wind, RD(K.wx.n), wx, wy, C.CW);
             C.wi = wx.i; C.wj = wy.i;
         }
         gather<R, 4, kThermoStride, Wd::T>(thermo, RD(K.tx.n), tx, ty, CT);
         SL.issue(K, lon, lat);
-#endif
     }
 
     __device__ __forceinline__ void track(const CornerCacheT<R> &C, const EvalKT<R> &K, double t, R lon, R lat, R v,

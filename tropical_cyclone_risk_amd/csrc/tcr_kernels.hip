@@ -355,11 +355,6 @@ __global__ __launch_bounds__(64 * kFsMfmaWaves, TCR_FS_MFMA_WPS) void k_fourier_
     double *const stg = stage[wave];
     auto epilogue_piece = [&](int piece) {
         if (!ep.live) return;                                   // wave-uniform
-#if defined(TCR_FS_ABLATE) && (TCR_FS_ABLATE & 8)
-        // timing experiment: the store pattern alone (no scaling, no LDS staging; table contents wrong)
-        if (sizeof(R) == 8 && piece != 5 && piece != 6) return;
-        if (sizeof(R) == 8) { ep.d0 = make_double2(ep.v[0], ep.v[1]); ep.d1 = make_double2(ep.v[2], ep.v[3]); }
-#endif
         if (sizeof(R) == 8) {
             switch (piece) {
             case 0: ep.v[0] = amp * ep.v[0]; ep.v[1] = amp * ep.v[1]; ep.v[2] = amp * ep.v[2]; ep.v[3] = amp * ep.v[3]; break;
@@ -375,22 +370,9 @@ __global__ __launch_bounds__(64 * kFsMfmaWaves, TCR_FS_MFMA_WPS) void k_fourier_
                 const int64_t storm = i ? ep.s1 : ep.s0;
                 const int k = ep.k0 + ((lane & 31) >> 1);
                 const double2 d = i ? ep.d1 : ep.d0;
-#if defined(TCR_FS_ABLATE) && (TCR_FS_ABLATE & 1)
-                if (row < ne && k < ns && d.x == 1.2345e300)    // timing experiment: no stores
-#else
-                if (row < ne && k < ns)
-#endif
-                {
+                if (row < ne && k < ns) {
                     double *dst = reinterpret_cast<double *>(fs) + (storm * (int64_t)ns + ep.k0) * 4 + (lane & 31) * 2;
-#if defined(TCR_FS_NT) && TCR_FS_NT
-                    // experiment: streaming stores, so that the 0.95 GB table does not sweep the
-                    // field data out of the Infinity Cache on its way to HBM
-                    typedef double nt2 __attribute__((ext_vector_type(2)));
-                    nt2 v; v[0] = d.x; v[1] = d.y;
-                    __builtin_nontemporal_store(v, reinterpret_cast<nt2 *>(dst));
-#else
                     *reinterpret_cast<double2 *>(dst) = d;
-#endif
                 }
                 break;
             }
@@ -400,11 +382,7 @@ __global__ __launch_bounds__(64 * kFsMfmaWaves, TCR_FS_MFMA_WPS) void k_fourier_
             const int64_t row = ep.tile * 4 + q;
             const int64_t storm = ep.s0;
             const int k = ep.k0 + j;
-#if defined(TCR_FS_ABLATE) && (TCR_FS_ABLATE & 1)
-            if (row < ne && k < ns && ep.v[0] == 1.2345e300)
-#else
             if (row < ne && k < ns)
-#endif
                 store_fs<R>(fs + (storm * (int64_t)ns + k) * 4, amp * ep.v[0], amp * ep.v[1], amp * ep.v[2], amp * ep.v[3]);
         }
     };
@@ -445,11 +423,7 @@ __global__ __launch_bounds__(64 * kFsMfmaWaves, TCR_FS_MFMA_WPS) void k_fourier_
             D4 acc = D4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int ks = 0; ks < kFsMfmaKSteps; ++ks) {
-#if defined(TCR_FS_ABLATE) && (TCR_FS_ABLATE & 2)
-                acc[ks & 3] += A[ks] * B[t][ks];              // timing experiment: no matrix instructions (values wrong)
-#else
                 acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[ks], B[t][ks], acc, 0, 0, 0);
-#endif
                 epilogue_piece(ks);                              // of the previous tile
                 __builtin_amdgcn_sched_barrier(0);               // keep this interleaving
             }
@@ -523,21 +497,9 @@ constexpr int kWave = 64;
 #ifndef TCR_INT_WPS_F32
 #define TCR_INT_WPS_F32 1  // ... and the fp32 instantiation: budgeted for 2 it spills 248 B per lane and is slower (1.38 vs 1.29 ms per step)
 #endif
-#ifndef TCR_INT_PIPELINE
-#define TCR_INT_PIPELINE 0   // 1: the next stage point's gathers are issued ahead of the intensity half (measured: +4 % time)
-#endif
 constexpr int kRunning = 99;
 constexpr int kIntSlotCache = 32;     // field-slot pointers kept in LDS by k_integrate
 template <typename R> constexpr int int_wps() { return sizeof(R) == 8 ? TCR_INT_WPS : TCR_INT_WPS_F32; }
-// Register cap of the integrator (build knob for the experiment in DESIGN.md §9): amdgpu_num_vgpr(N) makes the kernel
-// allocate 256 + (2N - 256) registers of the SIMD's 512, so that the small kernels of the batches other streams have in
-// flight (Fourier table, post-processing: 64-96 registers) could be resident on the same SIMD and issue in the
-// integrator's stalls.  Measured: the spills cost more than the overlap gains (N = 224 / 208 / 192: +4 % / 0 / +20 % per step).
-#ifdef TCR_INT_NUM_VGPR
-#define TCR_INT_CAP __attribute__((amdgpu_num_vgpr(TCR_INT_NUM_VGPR)))
-#else
-#define TCR_INT_CAP
-#endif
 
 // k_integrate: the sequential part of a storm — RK45 steps until the terminal event.
 //
@@ -555,7 +517,7 @@ template <typename R> constexpr int int_wps() { return sizeof(R) == 8 ? TCR_INT_
 // is accumulated in fp64 from the fp32 stage derivatives, and err < 1, the factor 0.9 err^-0.2 and the
 // min-step test are the fp64 expressions of the fp64 build (every (double) cast below is the identity there).
 template <typename R, bool AFFINE, bool PROBE, int SM>
-__global__ __launch_bounds__(kWave, (int_wps<R>())) TCR_INT_CAP void k_integrate(KArgsT<R> a)
+__global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a)
 {
     // TCR_FUSE_RK (tcr_device.h): stage inputs, y_new, the error norm and the initial-step norms below contract to fmas; the
     // in-flight 2-day sample does not (k_screen must reproduce it bit for bit), nor does anything inlined from another function
@@ -601,8 +563,7 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) TCR_INT_CAP void k_integrate
     CornerCacheT<R> CC;
     cache_reset(CC);
     RhsPipeT<R, AFFINE, SM> PIPE;
-    bool pre = false;                       // the gathers of the point (e, et) are already in flight
-    double etn = 0;
+    double etn = 0;                         // the time of the next stage point
 
     auto finalize = [&]() {
         a.n_valid[sid] = next_out;
@@ -662,16 +623,6 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) TCR_INT_CAP void k_integrate
     // occupancy accounting lives in LDS (lane 0 only): the kernel has no register to spare
     __shared__ unsigned long long occ[4];
     if (lane == 0) { occ[0] = 0; occ[1] = 0; occ[2] = wall_clock64(); occ[3] = clock64(); }
-#ifdef TCR_INT_PHASE_CLOCKS
-    // experiment of DESIGN.md §9: shader clocks per phase of an evaluation slot, lane 0 of block 0 (perturbs the schedule)
-    __shared__ unsigned long long ph[8];
-    if (lane == 0) for (int i = 0; i < 8; ++i) ph[i] = 0;
-    unsigned long long ph_last = clock64();
-#define TCR_PHASE_CLK(i) do { if (TCR_INT_PHASE_CLOCKS == 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long now_ = clock64(); \
-        if (lane == 0) { ph[i] += now_ - ph_last; if ((i) == 0) ph[5] += 1; } ph_last = now_; } while (0)
-#else
-#define TCR_PHASE_CLK(i) do { } while (0)
-#endif
     for (;;) {
         // ---- cycle boundary.  First launch of a chain with a segmented forcing table: a storm whose next attempt would read
         // the table beyond the part written so far leaves for the next pass (its lane takes a new storm right away)
@@ -754,26 +705,16 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) TCR_INT_CAP void k_integrate
         for (int slot = 0; slot < 6; ++slot) {
             const bool live = active && !(fresh && slot >= 2);
             RhsT<R> r{};
-#if defined(TCR_K_KERNARG)
-            const EvalKT<R> &Kq = a.K;           // experiment: constants through scalar loads from the kernel arguments
-#elif defined(TCR_OPAQUE_K)
-            int koff = 0;
-            asm volatile("" : "+s"(koff));      // opaque per iteration: the ~100 EvalK constants stay in LDS instead of being hoisted into registers
-            const EvalKT<R> &Kq = *reinterpret_cast<const EvalKT<R> *>(reinterpret_cast<const char *>(&K) + koff);
-#else
-            const EvalKT<R> &Kq = K;
-#endif
-            // Software pipeline over the stages of an attempt: the next stage *point* needs only this evaluation's
-            // d lon/dt and d lat/dt, so its gathers are issued as soon as those exist and the intensity half of this
-            // evaluation runs in their shadow.  Exposed round trips remain at the first slot of a cycle (the point
-            // depends on the step-size decision) and for fresh storms.
-            TCR_PHASE_CLK(0);
-            if (live && !pre) PIPE.issue(CC, Kq, wind, thermo, fs, et, e[0], e[1]);
-            TCR_PHASE_CLK(1);
+            // the ~100 evaluation constants come through scalar loads from the kernel arguments, not from the LDS copy K
+            // (round 6: chain -3 %, 100 000-storm step -1.5 %, bit-identical)
+            const EvalKT<R> &Kq = a.K;
+            // Each slot issues the gathers of its own evaluation point (e, et) at its start and waits for them in the track
+            // half; the intensity half follows.  (Issuing the next point's gathers ahead of the intensity half instead was
+            // measured slower or no better)
+            if (live) PIPE.issue(CC, Kq, wind, thermo, fs, et, e[0], e[1]);
             R th[4] = {0, 0, 0, 0}, lb[2] = {0, 0};
             TrackMidT<R> mid{};
             if (live) PIPE.track(CC, Kq, et, e[0], e[1], e[2], r, mid, th, lb);
-            TCR_PHASE_CLK(2);
             // rk_step (rk.py:62-70): K[s] = fun(...); next stage input dy = dot(K[:s].T, a[:s]) * h, one component at a time
             R en[4] = {e[0], e[1], e[2], e[3]};
             auto stage_input = [&](int i) {
@@ -793,16 +734,12 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) TCR_INT_CAP void k_integrate
             };
             const bool stepping = live && !fresh;
             const R v_e = e[2], m_e = e[3], lat_e = e[1];
-            pre = false;
             if (stepping) { KS(slot + 1, 0) = r.d[0]; KS(slot + 1, 1) = r.d[1]; }
             if (stepping && slot < 5) {
                 stage_input(0); stage_input(1);
                 etn = (slot < 4) ? t + RK_C[slot + 2] * h : t + h;
-                if (TCR_INT_PIPELINE) { PIPE.issue(CC, Kq, wind, thermo, fs, etn, en[0], en[1]); pre = true; }
             }
-            TCR_PHASE_CLK(3);
             if (live) rhs_intensity<R>(Kq, ck_h, lat_e, v_e, m_e, th, lb, mid, r);
-            TCR_PHASE_CLK(4);
             if (PROBE && live) {
                 const int ev = fresh ? slot : nfev;          // index of this evaluation in the storm's call order
                 if (ev < a.probe_cap) a.probe[(size_t)sid * a.probe_cap + ev] = (uint8_t)r.dec;
@@ -831,11 +768,7 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) TCR_INT_CAP void k_integrate
                         if (rejected && fac > 1) fac = 1;
                         ha *= fac;
                         // step record for k_emit: doubles t_old, h, t_new, -; then R y_old[4], K[7][4]
-#ifdef TCR_ABLATE_STEP_STORES
-                        if (nacc < 0) {         // timing experiment only: no step records (post-processing reads garbage)
-#else
                         if (nacc < a.max_rk_steps && !doomed) {
-#endif
                             double *rec = srec + (size_t)nacc * REC;
                             double2 *o = reinterpret_cast<double2 *>(rec);
                             o[0] = make_double2(t, h);
@@ -947,11 +880,6 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) TCR_INT_CAP void k_integrate
         }
         fresh = false;
     }
-#ifdef TCR_INT_PHASE_CLOCKS
-    if (lane == 0 && blockIdx.x == 0 && a.pass == 0)
-        printf("phase clocks (block 0, pass 0): issue %llu track %llu stage+prefetch %llu intensity %llu bookkeeping %llu; slots %llu\n",
-               ph[1], ph[2], ph[3], ph[4], ph[0], ph[5]);
-#endif
     if (lane == 0) {       // occupancy accounting of this pass (tcr_integrate_pass_stats)
         unsigned long long *st = a.queue + 2 * kMaxPasses + 4 * a.pass;
         atomicAdd(st + 0, occ[0]);
@@ -1199,17 +1127,9 @@ __global__ __launch_bounds__(kPostThreads, TCR_SHADOW_WPS) void k_emit(EArgsT<R>
         R ye[4] = {0, 0, 0, 0}, w[4] = {0, 0, 0, 0};
         if (valid) {
             const double te = ts_at(P, i);
-    #if defined(TCR_EMIT_ABLATE) && (TCR_EMIT_ABLATE & 1)
-            ye[0] = R(-60) + R(0.05) * (R)i; ye[1] = R(15) + R(0.03) * (R)i; ye[2] = R(20); ye[3] = R(0.5) + R(1e-3) * (R)my_step;     // timing experiment: no record gather
-    #else
             dense_at<R, 4>(srec_storm, my_step, te, ye);
-    #endif
             const R *wind = (slot_id < kEmitSlotCache) ? s_wind[slot_id] : slot_wind<R>(a.D.slots[slot_id]);
-    #if defined(TCR_EMIT_ABLATE) && (TCR_EMIT_ABLATE & 2)
-            w[0] = ye[0] * R(0.1); w[1] = ye[1] * R(0.1); w[2] = R(1); w[3] = (R)(wind != nullptr);            // timing experiment: no wind / forcing gathers
-    #else
             env_winds<R, AFFINE>(K, wind, a.fs + sid * ns * 4, ye[0], ye[1], te, w);
-    #endif
             a.lon[o] = ye[0]; a.lat[o] = ye[1]; a.v[o] = ye[2]; a.m[o] = ye[3];
             V4 wv; wv[0] = w[0]; wv[1] = w[1]; wv[2] = w[2]; wv[3] = w[3];
             *reinterpret_cast<V4 *>(a.envw + o * 4) = wv;
@@ -1332,9 +1252,6 @@ __global__ __launch_bounds__(kScreenThreads, TCR_SHADOW_WPS) void k_screen(EArgs
         if (s.i_lo <= j2d + 1 && j2d + 1 < s.i_hi) cap[g][1] = v_at(s, j2d + 1);
         if (s.i_lo <= n - 1 && n - 1 < s.i_hi) cap[g][2] = v_at(s, n - 1);
     };
-#if defined(TCR_SCREEN_ABLATE) && TCR_SCREEN_ABLATE == 2
-    n = 0;
-#endif
     const bool has0 = l < nst && n > 0;
     StepV s0{};                                          // the lane's first step stays in registers for phase 2
     if (has0) { s0 = load_step(l); caps(s0); }
@@ -1347,9 +1264,6 @@ __global__ __launch_bounds__(kScreenThreads, TCR_SHADOW_WPS) void k_screen(EArgs
         else v2d = interp_v2d<R>(cap[g][0], cap[g][1], ts_at(P, j2d), ts_at(P, j2d + 1), t2d);
         pass2d = v2d >= P.v_2d_thresh;
     }
-#if defined(TCR_SCREEN_ABLATE)
-    pass2d = false;
-#endif
     // ---- phase 2: `any(v >= v_thresh)` over the hourly samples, only for the storms that passed.
     // A step whose dense output cannot reach the threshold anywhere is skipped without looking at its samples:
     // on x in [0, 1] every term Q_k x^(k+1) is at most max(Q_k, 0), so v <= y0 + |h| sum max(Q_k, 0) (h > 0 here); the
