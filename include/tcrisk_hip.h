@@ -561,6 +561,50 @@ int tcr_landfall_dev(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, int32_t max_
 int tcr_landfall_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, int32_t max_events, int32_t *n_landfall, int32_t *ev_k,
                       double *ev_lon, double *ev_lat, double *ev_v, double *ev_v_inland, uint8_t *flags);
 
+/* ---- track climatology: track, exceedance, genesis and LMI density, PDI -------------------------------------------- */
+/* replaces: nothing in the reference's code (its README's track density, genesis locations, LMI distributions and
+ * power dissipation, which users compute in NumPy over the track planes).  A sample is live when lon and lat are not NaN.
+ *   grid            tcr_clim_grid: dlon, dlat > 0, nlon, nlat >= 1, nlon * dlon <= 360, nlon * nlat < 2^31, all finite.
+ *                   Longitude: t = fmod(x - lon0, 360), t += 360 when t < 0, t = 0 when that rounds to 360, i = floor(t / dlon);
+ *                   a global grid (nlon * dlon == 360 exactly) clamps i to nlon - 1, any other grid leaves i >= nlon outside.
+ *                   Latitude: j = floor((y - lat0) / dlat), inside iff 0 <= j < nlat.  The cell is this arithmetic, so tracks
+ *                   in either longitude convention (or lon > 360) land in the same cell.  Cell (j, i) is j * nlon + i.
+ *   q(v)            (int64) rint(((v * v) * v) * 1024.0) in fp64 without contraction for 0 <= v <= 400, else 0; the physical
+ *                   PDI is q / 1024 * dt (m^3 s^-2, dt the sample spacing).  Integer sums: bit-identical whatever the launch
+ *                   shape and the storm order.
+ * Maps, [n_group][nlat][nlon], overwritten by every call, of the storms s with group[s] in [0, n_group):
+ *   track (int32)   storms with at least one live sample in the cell (once per cell, however often the storm comes back)
+ *   exceed (int32)  [n_group][n_bin][nlat][nlon]: storms whose NaN-skipping max of vmax over their live samples in the cell
+ *                   is >= thresholds[b] (NULL when n_bin == 0)
+ *   genesis (int32) storms whose first live sample is in the cell
+ *   lmi (int32)     storms whose lifetime-maximum sample is in the cell: the first sample attaining the NaN-skipping max of
+ *                   vmax over the storm's live samples
+ *   pdi (int64)     sum of q(vmax) over the live samples in the cell
+ * Per storm, [n_trk]: genesis_k (int32, the first live sample, -1 when none), lmi_v (the lifetime maximum, NaN when no live
+ * sample has a non-NaN vmax), lmi_k (int32, its sample, -1 when none), pdi_storm (int64, q summed over the live samples).
+ * Samples outside the grid add nothing to the maps but count in the per-storm outputs; a storm whose group is out of range adds
+ * nothing to the maps.  Samples are points: a storm can step over a cell smaller than an hour's motion without a sample in it.
+ * Arguments: n_trk >= 0, 1 <= n_t, row_stride >= n_t, n_trk * n_t <= 2^27 (the int64 sums cannot overflow), n_group >= 1,
+ * 0 <= n_bin <= 64, thresholds (host) finite and strictly ascending.  The tracks' group fields are ignored.  n_trk == 0 zeroes
+ * the maps and writes nothing else.  _dev: tracks, group and outputs are device memory, asynchronous on `stream`; tracks longer
+ * than 512 samples sort in a workspace of the context (grown on demand): calls on one context must be ordered. */
+typedef struct {
+    double lon0, dlon, lat0, dlat;
+    int64_t nlon, nlat;
+} tcr_clim_grid;
+typedef struct {
+    int32_t *track, *exceed, *genesis, *lmi;   /* [n_group][nlat][nlon]; exceed [n_group][n_bin][nlat][nlon] */
+    int64_t *pdi;                              /* [n_group][nlat][nlon] */
+    int32_t *genesis_k;                        /* [n_trk] */
+    double *lmi_v;                             /* [n_trk] */
+    int32_t *lmi_k;                            /* [n_trk] */
+    int64_t *pdi_storm;                        /* [n_trk] */
+} tcr_clim_out;
+int tcr_climatology_dev(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const int32_t *group, int32_t n_group,
+                        const tcr_clim_grid *grid, int32_t n_bin, const double *thresholds, const tcr_clim_out *out, void *stream);
+int tcr_climatology_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const int32_t *group, int32_t n_group,
+                         const tcr_clim_grid *grid, int32_t n_bin, const double *thresholds, const tcr_clim_out *out);
+
 #ifdef __cplusplus
 }
 #endif

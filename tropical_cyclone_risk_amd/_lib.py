@@ -37,7 +37,7 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_probe_math_host', 'tcr_comm_unique_id', 'tcr_comm_create', 'tcr_comm_destroy', 'tcr_comm_rank', 'tcr_comm_world', 'tcr_allgather_dev',
            'tcr_allgather_rows_dev', 'tcr_allgather_counts_dev', 'tcr_allreduce_sum_i64_dev', 'tcr_concat_rows_dev',
            'tcr_hazard_dev', 'tcr_hazard_host', 'tcr_hazard_pairs', 'tcr_land_upload', 'tcr_land_info', 'tcr_landfall_dev',
-           'tcr_landfall_host')
+           'tcr_landfall_host', 'tcr_climatology_dev', 'tcr_climatology_host')
 TCR_COMM_ID_BYTES = 128
 
 
@@ -109,6 +109,17 @@ class HazardTracks(C.Structure):
 class LandGrid(C.Structure):
     """tcr_land_grid: the land grid of tcr_land_upload (host memory)."""
     _fields_ = [('nlon', C.c_int64), ('nlat', C.c_int64), ('lon', C.c_void_p), ('lat', C.c_void_p), ('land', C.c_void_p)]
+
+
+class ClimGrid(C.Structure):
+    """tcr_clim_grid: the cell grid of tcr_climatology_*."""
+    _fields_ = [('lon0', C.c_double), ('dlon', C.c_double), ('lat0', C.c_double), ('dlat', C.c_double), ('nlon', C.c_int64),
+                ('nlat', C.c_int64)]
+
+
+class ClimOut(C.Structure):
+    """tcr_clim_out: the output planes of tcr_climatology_* (maps [n_group][nlat][nlon], per storm [n_trk])."""
+    _fields_ = [(k, C.c_void_p) for k in ('track', 'exceed', 'genesis', 'lmi', 'pdi', 'genesis_k', 'lmi_v', 'lmi_k', 'pdi_storm')]
 
 
 class TcrError(RuntimeError):
@@ -238,6 +249,9 @@ def lib():
     L.tcr_land_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     L.tcr_landfall_dev.argtypes = [C.c_void_p, C.POINTER(HazardTracks), C.c_int32] + [C.c_void_p] * 8
     L.tcr_landfall_host.argtypes = [C.c_void_p, C.POINTER(HazardTracks), C.c_int32] + [C.c_void_p] * 7
+    L.tcr_climatology_dev.argtypes = [C.c_void_p, C.POINTER(HazardTracks), C.c_void_p, C.c_int32, C.POINTER(ClimGrid), C.c_int32, DP,
+                                      C.POINTER(ClimOut), C.c_void_p]
+    L.tcr_climatology_host.argtypes = L.tcr_climatology_dev.argtypes[:-1]
     if L.tcr_abi_version() != TCR_ABI_VERSION:
         raise TcrError('libtcrisk_hip.so ABI version %d != binding version %d'
                        % (L.tcr_abi_version(), TCR_ABI_VERSION))

@@ -228,6 +228,9 @@ struct tcr_ctx {
     int64_t lf_nlon = 0, lf_nlat = 0;
     bool lf_periodic = false;
     double lf_guess[4] = {0, 0, 0, 0};              // lon0, (nlon - 1) / lon span, lat0, (nlat - 1) / lat span
+    // track climatology (tcr_climatology.hip): key workspace of tracks longer than the kernel's LDS slice
+    void *d_cl = nullptr;
+    size_t cl_cap = 0;
 };
 
 namespace {
@@ -1094,6 +1097,7 @@ int tcr_ctx_destroy(tcr_ctx *ctx)
     if (ctx->hz_ev) (void)hipEventDestroy(ctx->hz_ev);
     if (ctx->hz_done) (void)hipEventDestroy(ctx->hz_done);
     (void)hipFree(ctx->lf_xy); (void)hipFree(ctx->lf_bits);
+    (void)hipFree(ctx->d_cl);
     for (int i = 0; i < 2; ++i) { if (ctx->h_stage[i]) (void)hipHostFree(ctx->h_stage[i]); if (ctx->h_stage_ev[i]) (void)hipEventDestroy(ctx->h_stage_ev[i]); }
     (void)hipFree(ctx->d_hist_partial); (void)hipFree(ctx->d_cell); (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_tc_idx); (void)hipFree(ctx->d_tc_count); (void)hipFree(ctx->d_queue); (void)hipFree(ctx->d_sidx); (void)hipFree(ctx->d_park[0]); (void)hipFree(ctx->d_park[1]); (void)hipFree(ctx->d_sc_table); (void)hipFree(ctx->d_pf); (void)hipFree(ctx->d_screen_skip); (void)hipFree(ctx->d_und_list); (void)hipFree(ctx->d_und_count); (void)hipFree(ctx->d_tab);
     (void)hipStreamDestroy(ctx->stream);
@@ -2325,3 +2329,4 @@ int tcr_round_graph_stats(tcr_ctx *ctx, int64_t *n_graphs, int64_t *n_replays)
 #include "tcr_comm.hip"                  // multi-GPU exchange (RCCL, loaded at run time)
 #include "tcr_hazard.hip"                // site wind hazard (near-site intensity, exceedance counts)
 #include "tcr_landfall.hip"              // landfall detection (sea -> land steps of the model's land decision)
+#include "tcr_climatology.hip"           // track climatology (track, exceedance, genesis, LMI density and PDI per cell)

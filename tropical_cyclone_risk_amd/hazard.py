@@ -264,14 +264,18 @@ def collect_sites(args):
     return np.array(lon, dtype=np.float64), np.array(lat, dtype=np.float64)
 
 
-def load_groups(files):
+def load_groups(files, extra=()):
     """Read the track files and number their (file, year) groups: every year of every file's `year` coordinate is one group,
     years without storms included.  Returns lon, lat, vmax [n_trk][n_t], the group of every storm, group_file and group_year
-    [n_group] (the group -> (file index, year) map)."""
+    [n_group] (the group -> (file index, year) map).  extra: names of further variables of the files; when given, a seventh
+    element {name: [one array per file]} follows."""
     from . import io as tio
     lon, lat, vmax, groups, gfile, gyear = [], [], [], [], [], []
+    more = {name: [] for name in extra}
     for k, fn in enumerate(files):
         d = tio.read_tracks(fn)
+        for name in extra:
+            more[name].append(np.asarray(d[name]))
         years = np.asarray(d['year']).astype(np.int64).reshape(-1)
         tc_years = np.asarray(d['tc_years']).astype(np.int64).reshape(-1)
         pos = {int(y): i for i, y in enumerate(years)}
@@ -285,8 +289,9 @@ def load_groups(files):
     n_t = {a.shape[1] for a in lon}
     if len(n_t) != 1:
         raise ValueError('the track files have different time axes: %s' % sorted(n_t))
-    return (np.concatenate(lon), np.concatenate(lat), np.concatenate(vmax), np.concatenate(groups),
-            np.array(gfile, dtype=np.int64), np.array(gyear, dtype=np.int64))
+    res = (np.concatenate(lon), np.concatenate(lat), np.concatenate(vmax), np.concatenate(groups),
+           np.array(gfile, dtype=np.int64), np.array(gyear, dtype=np.int64))
+    return res + (more,) if extra else res
 
 
 def main(argv=None):
