@@ -605,6 +605,54 @@ int tcr_climatology_dev(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const int
 int tcr_climatology_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const int32_t *group, int32_t n_group,
                          const tcr_clim_grid *grid, int32_t n_bin, const double *thresholds, const tcr_clim_out *out);
 
+/* ---- wind footprint: peak wind at sites from a radial profile around the centre ---------------------------------- */
+/* replaces: nothing in the reference's code; extends its axi_to_max_wind (wind/tc_wind.py) from one number per sample to the
+ * wind each sample produces at each site.  R = 6378.1 km (util/constants.py earth_R), Omega = 7.292e-5 s^-1, SI units.
+ *   track           a storm's leading run of n samples where lon, lat, v, u250, v250, u850, v850 are all finite (later samples
+ *                   are ignored).  A track of one sample has no translation speed and contributes nothing.
+ *   per sample k    (ut, vt) of calc_translational_speed (util/sphere.py, linear extrapolation at both ends, dt = dt_s) in the
+ *                   operation order of the pipeline's vmax_trks; G, Ui, Vi, |U|, fac = min(1, 0.5 v / |U|) as tc_wind.py:7-16,
+ *                   A = fac (Ui, Vi).  rm (km) = rmax_km[k] when the plane is given, else rmax_const_km when > 0, else
+ *                   Willoughby, Darling & Rahn (2006, eq. 7a) 46.4 exp(-0.0155 v + 0.0169 |lat|).  f = 2 Omega |sin lat|,
+ *                   Mm = rm v + f rm^2 / 2.
+ *   sub-steps       substeps = n >= 1: between track samples k and k + 1, sub-samples at tau = j / n, j = 1 .. n - 1, with lat, v,
+ *                   rm and both components of A linear in tau (y_k + tau (y_k+1 - y_k)), lon the same with its difference reduced
+ *                   to [-180, 180); f and Mm from the interpolated values.
+ *   per (site, s)   r = haversine distance with R; the sample is included iff r <= r_out_km.  c = ck_cd, x = r / rm,
+ *                   ratio = [2 x^2 / (2 - c + c x^2)]^(1 / (2 - c)) (Emanuel & Rotunno 2011, eq. 36),
+ *                   V = max(0, (Mm ratio - f r^2 / 2) / r), V = 0 at r = 0; V(rm) = v.  d = (e, n) / |(e, n)| with
+ *                   e = cos phi_s sin(lam_s - lam_c), n = cos phi_c sin phi_s - sin phi_c cos phi_s cos(lam_s - lam_c);
+ *                   t = h (-d_n, d_e), h = +1 for lat >= 0 and -1 otherwise; wind = |V t + (V / v) A|, 0 when v <= 0.
+ *                   At r = rm its maximum over azimuth is v + fac |U|, axi_to_max_wind's vmax.
+ *   site_max        [n_site][n_trk] (optional, NULL: not written): max of the wind over the included samples and sub-samples of
+ *                   the storm, NaN when none is included.
+ *   counts          [n_site][n_group][n_bin] (int32): storms s in [group_off[g], group_off[g + 1]) with site_max >= thresholds[b].
+ * Arguments: dt_s > 0, 0 < ck_cd < 2, 0 < r_out_km <= 2000, 1 <= substeps <= 64, rmax_const_km >= 0 (0 when the plane is given),
+ * 1 <= n_bin <= 64, thresholds finite and strictly ascending, group_off non-decreasing from 0 to n_trk; rm > 0 and finite at
+ * every sample of a track (tcr_windfield_host checks the plane; tcr_windfield_dev cannot, and drops a storm with a bad rm:
+ * NaN at every site, counted nowhere).  Results are a max of per-pair values and integer counts: bit-identical from run to run,
+ * whatever the launch shape, the site order or the storm order.  Sites in a spatially coherent order (runs of 64 neighbours)
+ * run fastest.  _dev: planes, sites, counts and site_max are device memory, asynchronous on `stream`; group_off and thresholds
+ * are host memory in both entry points.  Workspaces belong to the context (grown on demand): calls on one context must be
+ * ordered (one stream, or the previous call finished). */
+typedef struct {
+    int64_t n_trk, n_t, row_stride;
+    const double *lon, *lat, *v, *u250, *v250, *u850, *v850;
+    const double *rmax_km;                 /* [n_trk][row_stride] in km, or NULL */
+    int32_t n_group;
+    const int64_t *group_off;              /* host, [n_group + 1] */
+} tcr_wind_tracks;
+typedef struct {
+    double dt_s, ck_cd, r_out_km, rmax_const_km;
+    int32_t substeps;
+} tcr_wind_params;
+int tcr_windfield_dev(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_wind_params *prm, int64_t n_site, const double *site_lon,
+                      const double *site_lat, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_max, void *stream);
+int tcr_windfield_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_wind_params *prm, int64_t n_site, const double *site_lon,
+                       const double *site_lat, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_max);
+/* (site, sample or sub-sample) pairs the last tcr_windfield_* call of this context evaluated after culling; waits for that call */
+int tcr_windfield_pairs(tcr_ctx *ctx, int64_t *pairs);
+
 #ifdef __cplusplus
 }
 #endif

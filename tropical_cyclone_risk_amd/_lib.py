@@ -37,7 +37,8 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_probe_math_host', 'tcr_comm_unique_id', 'tcr_comm_create', 'tcr_comm_destroy', 'tcr_comm_rank', 'tcr_comm_world', 'tcr_allgather_dev',
            'tcr_allgather_rows_dev', 'tcr_allgather_counts_dev', 'tcr_allreduce_sum_i64_dev', 'tcr_concat_rows_dev',
            'tcr_hazard_dev', 'tcr_hazard_host', 'tcr_hazard_pairs', 'tcr_land_upload', 'tcr_land_info', 'tcr_landfall_dev',
-           'tcr_landfall_host', 'tcr_climatology_dev', 'tcr_climatology_host')
+           'tcr_landfall_host', 'tcr_climatology_dev', 'tcr_climatology_host', 'tcr_windfield_dev', 'tcr_windfield_host',
+           'tcr_windfield_pairs')
 TCR_COMM_ID_BYTES = 128
 
 
@@ -120,6 +121,19 @@ class ClimGrid(C.Structure):
 class ClimOut(C.Structure):
     """tcr_clim_out: the output planes of tcr_climatology_* (maps [n_group][nlat][nlon], per storm [n_trk])."""
     _fields_ = [(k, C.c_void_p) for k in ('track', 'exceed', 'genesis', 'lmi', 'pdi', 'genesis_k', 'lmi_v', 'lmi_k', 'pdi_storm')]
+
+
+class WindTracks(C.Structure):
+    """tcr_wind_tracks: the track planes of tcr_windfield_* (rmax_km optional) and the storm groups (group_off is host memory)."""
+    _fields_ = [('n_trk', C.c_int64), ('n_t', C.c_int64), ('row_stride', C.c_int64)] + \
+        [(k, C.c_void_p) for k in ('lon', 'lat', 'v', 'u250', 'v250', 'u850', 'v850', 'rmax_km')] + \
+        [('n_group', C.c_int32), ('group_off', C.POINTER(C.c_int64))]
+
+
+class WindParams(C.Structure):
+    """tcr_wind_params: sample spacing, Ck / Cd, outer radius, constant rm (0: modelled) and sub-steps of tcr_windfield_*."""
+    _fields_ = [('dt_s', C.c_double), ('ck_cd', C.c_double), ('r_out_km', C.c_double), ('rmax_const_km', C.c_double),
+                ('substeps', C.c_int32)]
 
 
 class TcrError(RuntimeError):
@@ -252,6 +266,10 @@ def lib():
     L.tcr_climatology_dev.argtypes = [C.c_void_p, C.POINTER(HazardTracks), C.c_void_p, C.c_int32, C.POINTER(ClimGrid), C.c_int32, DP,
                                       C.POINTER(ClimOut), C.c_void_p]
     L.tcr_climatology_host.argtypes = L.tcr_climatology_dev.argtypes[:-1]
+    L.tcr_windfield_dev.argtypes = [C.c_void_p, C.POINTER(WindTracks), C.POINTER(WindParams), C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_int32, DP, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tcr_windfield_host.argtypes = L.tcr_windfield_dev.argtypes[:-1]
+    L.tcr_windfield_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     if L.tcr_abi_version() != TCR_ABI_VERSION:
         raise TcrError('libtcrisk_hip.so ABI version %d != binding version %d'
                        % (L.tcr_abi_version(), TCR_ABI_VERSION))

@@ -231,6 +231,14 @@ struct tcr_ctx {
     // track climatology (tcr_climatology.hip): key workspace of tracks longer than the kernel's LDS slice
     void *d_cl = nullptr;
     size_t cl_cap = 0;
+    // wind footprint (tcr_windfield.hip): records, caps, record counts, partial counts, chunk table, staged samples; the pinned
+    // staging of the chunk table
+    void *d_wf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t wf_cap[6] = {0, 0, 0, 0, 0, 0};
+    int64_t *wf_h = nullptr;
+    size_t wf_h_cap = 0;
+    hipEvent_t wf_ev = nullptr, wf_done = nullptr;  // chunk table uploaded / last call done
+    unsigned long long *wf_pairs = nullptr;         // pairs the last call evaluated (inside d_wf[4])
 };
 
 namespace {
@@ -1098,6 +1106,10 @@ int tcr_ctx_destroy(tcr_ctx *ctx)
     if (ctx->hz_done) (void)hipEventDestroy(ctx->hz_done);
     (void)hipFree(ctx->lf_xy); (void)hipFree(ctx->lf_bits);
     (void)hipFree(ctx->d_cl);
+    for (void *p : ctx->d_wf) (void)hipFree(p);
+    if (ctx->wf_h) (void)hipHostFree(ctx->wf_h);
+    if (ctx->wf_ev) (void)hipEventDestroy(ctx->wf_ev);
+    if (ctx->wf_done) (void)hipEventDestroy(ctx->wf_done);
     for (int i = 0; i < 2; ++i) { if (ctx->h_stage[i]) (void)hipHostFree(ctx->h_stage[i]); if (ctx->h_stage_ev[i]) (void)hipEventDestroy(ctx->h_stage_ev[i]); }
     (void)hipFree(ctx->d_hist_partial); (void)hipFree(ctx->d_cell); (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_tc_idx); (void)hipFree(ctx->d_tc_count); (void)hipFree(ctx->d_queue); (void)hipFree(ctx->d_sidx); (void)hipFree(ctx->d_park[0]); (void)hipFree(ctx->d_park[1]); (void)hipFree(ctx->d_sc_table); (void)hipFree(ctx->d_pf); (void)hipFree(ctx->d_screen_skip); (void)hipFree(ctx->d_und_list); (void)hipFree(ctx->d_und_count); (void)hipFree(ctx->d_tab);
     (void)hipStreamDestroy(ctx->stream);
@@ -2330,3 +2342,4 @@ int tcr_round_graph_stats(tcr_ctx *ctx, int64_t *n_graphs, int64_t *n_replays)
 #include "tcr_hazard.hip"                // site wind hazard (near-site intensity, exceedance counts)
 #include "tcr_landfall.hip"              // landfall detection (sea -> land steps of the model's land decision)
 #include "tcr_climatology.hip"           // track climatology (track, exceedance, genesis, LMI density and PDI per cell)
+#include "tcr_windfield.hip"             // wind footprint (peak wind at sites from a radial profile, exceedance counts)

@@ -1,0 +1,244 @@
+"""Wind footprints: the peak wind every storm of a track ensemble produces at every site, and its return periods.
+
+Each sample of a track is a vortex: the Emanuel & Rotunno (2011) radial profile of the azimuthal-mean wind ``v_trks`` around the
+centre, with radius of maximum wind ``rm`` (given, or Willoughby, Darling & Rahn 2006), plus the asymmetry of the model's own
+``axi_to_max_wind`` (translation speed and shear, ``wind/tc_wind.py``), so that at ``r = rm`` on the azimuth of maximum wind the
+footprint is the pipeline's ``vmax_trks``.  On the GPU (``csrc/tcr_windfield.hip``), for many sites at once:
+
+1. for each storm, the maximum over its samples (and linear sub-samples between them) within ``r_out_km`` of a site of the wind
+   that sample produces there (NaN when there are none);
+2. per group of storms (a year, or an (ensemble file, year) pair), the number of storms whose peak is ``>= v`` for ascending
+   thresholds ``v``;
+3. the return period ``total_years / exceedance_count`` (``hazard.return_periods``).
+
+The contract is the header's "wind footprint" section (include/tcrisk_hip.h).
+
+    python -m tropical_cyclone_risk_amd.windfield TRACKS.nc [TRACKS_e0.nc ...] --site=-80.1918,25.7617 --out wind.npz
+"""
+import argparse
+import ctypes as C
+import sys
+
+import numpy as np
+
+from . import _lib, hazard
+from .hazard import _Context, _is_tensor
+
+MAX_SUBSTEPS = 64
+MAX_R_OUT_KM = 2000.0
+
+
+def _default_ck_cd():
+    from . import namelist
+    return float(namelist.Ck) / float(namelist.Cd)
+
+
+def _track_length(planes, xp):
+    """[n_trk] length of the leading run of samples where every plane is finite."""
+    fin = planes[0] == planes[0]
+    for p in planes:
+        fin = fin & xp.isfinite(p)
+    n_t = int(fin.shape[1])
+    if xp is np:
+        return np.where(fin.all(axis=1), n_t, np.argmin(fin, axis=1))
+    f = fin.to(xp.int8)
+    return xp.where(fin.all(dim=1), xp.full_like(f[:, 0], n_t, dtype=xp.int64), f.argmin(dim=1))
+
+
+def site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt_s, rmax_km=None, ck_cd=None, r_out_km=500., substeps=1,
+              thresholds=hazard.DEFAULT_THRESHOLDS, return_max=False, engine=None, device=0, n_groups=None):
+    """Peak footprint wind and exceedance counts of every site.
+
+    lon, lat, v: [n_trk][n_t] fp64 (the track file's lon_trks, lat_trks, v_trks); env: (u250, v250, u850, v850), each [n_trk][n_t]
+    (the file's *_trks).  A storm's track is its leading run of samples where all seven are finite.  NumPy arrays or torch
+    tensors on the GPU (then everything stays there).  dt_s: the sample spacing (s).  rmax_km: None (Willoughby et al. 2006 from v
+    and lat), a scalar, or a [n_trk][n_t] plane (km, > 0 and finite on every track sample).  ck_cd: Ck / Cd of the profile, in
+    (0, 2) (None: the namelist's).  r_out_km: samples farther from a site do not count there, in (0, 2000].  substeps: 1..64
+    evaluation points per sample interval (linear sub-samples between samples).  groups, n_groups, site_lon / site_lat,
+    thresholds, return_max, engine, device: as hazard.site_hazard.  Returns a dict: ``counts`` [n_site][n_groups][n_bin] int32,
+    ``thresholds``, and with ``return_max`` ``site_max`` [n_site][n_trk] (m/s; NaN: no sample within r_out_km), in the type and
+    on the device of ``lon``.
+    """
+    torch_in = _is_tensor(lon)
+    if torch_in:
+        import torch
+        xp = torch
+        dev = lon.device
+        conv = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)     # noqa: E731
+        device = dev.index if dev.index is not None else torch.cuda.current_device()
+    else:
+        xp = np
+        conv = lambda a: np.asarray(a.cpu() if _is_tensor(a) else a, dtype=np.float64)   # noqa: E731
+    if len(env) != 4:
+        raise ValueError('env must be (u250, v250, u850, v850)')
+    planes = [conv(a) for a in (lon, lat, v) + tuple(env)]
+    site_lon, site_lat = (conv(a).reshape(-1) for a in (site_lon, site_lat))
+    if planes[0].ndim != 2 or any(tuple(p.shape) != tuple(planes[0].shape) for p in planes):
+        raise ValueError('lon, lat, v and the four env planes must be [n_trk][n_t] arrays of one shape')
+    n_trk, n_t = int(planes[0].shape[0]), int(planes[0].shape[1])
+    if n_t < 1:
+        raise ValueError('the tracks need at least one sample')
+    if site_lon.shape[0] != site_lat.shape[0] or site_lon.shape[0] < 1:
+        raise ValueError('site_lon and site_lat must be non-empty and of one length')
+    if not bool(xp.isfinite(site_lon).all()) or not bool(xp.isfinite(site_lat).all()):
+        raise ValueError('site coordinates must be finite')
+    dt_s = float(dt_s)
+    if not (np.isfinite(dt_s) and dt_s > 0):
+        raise ValueError('dt_s must be finite and > 0')
+    ck_cd = _default_ck_cd() if ck_cd is None else float(ck_cd)
+    if not 0.0 < ck_cd < 2.0:
+        raise ValueError('ck_cd must be in (0, 2)')
+    r_out_km = float(r_out_km)
+    if not 0.0 < r_out_km <= MAX_R_OUT_KM:
+        raise ValueError('r_out_km must be in (0, %g]' % MAX_R_OUT_KM)
+    if isinstance(substeps, bool) or int(substeps) != substeps or not 1 <= int(substeps) <= MAX_SUBSTEPS:
+        raise ValueError('substeps must be an integer in [1, %d]' % MAX_SUBSTEPS)
+    substeps = int(substeps)
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    if not 1 <= thr.size <= 64 or not np.isfinite(thr).all() or np.any(np.diff(thr) <= 0):
+        raise ValueError('thresholds must be 1 to 64 finite, strictly ascending values')
+    rm_const, rm_plane = 0.0, None
+    if rmax_km is not None:
+        if np.ndim(rmax_km.cpu() if _is_tensor(rmax_km) else rmax_km) == 0:
+            rm_const = float(rmax_km)
+            if not (np.isfinite(rm_const) and rm_const > 0):
+                raise ValueError('rmax_km must be finite and > 0')
+        else:
+            rm_plane = conv(rmax_km)
+            if tuple(rm_plane.shape) != (n_trk, n_t):
+                raise ValueError('an rmax_km plane must be [n_trk][n_t]')
+            n = _track_length(planes, xp)
+            ar = xp.arange(n_t, device=dev)[None, :] if torch_in else np.arange(n_t)[None, :]
+            used = (ar < n[:, None]) & (n[:, None] >= 2)
+            ok = xp.isfinite(rm_plane) & (rm_plane > 0)
+            if bool((used & ~ok).any()):
+                raise ValueError('rmax_km must be finite and > 0 at every sample of a track')
+    g = np.asarray(groups.cpu() if _is_tensor(groups) else groups).reshape(-1)
+    if g.shape[0] != n_trk or (n_trk and (g.dtype.kind not in 'iu' or g.min() < 0)):
+        raise ValueError('groups must hold one non-negative integer per storm')
+    g = g.astype(np.int64)
+    n_groups = int(n_groups if n_groups is not None else (g.max() + 1 if n_trk else 1))
+    if n_trk and g.max() >= n_groups:
+        raise ValueError('a group index is >= n_groups')
+    if n_groups < 1:
+        raise ValueError('n_groups must be >= 1')
+
+    # storms grouped contiguously (stable: storms keep their order inside a group), sites in spatial order
+    order = np.argsort(g, kind='stable')
+    group_off = np.zeros(n_groups + 1, dtype=np.int64)
+    group_off[1:] = np.cumsum(np.bincount(g, minlength=n_groups))
+    sorted_ = bool(np.all(order == np.arange(n_trk)))
+    site_order = hazard._spatial_order(site_lon, site_lat, xp)
+    n_site, n_bin = int(site_lon.shape[0]), int(thr.shape[0])
+    if rm_plane is not None:
+        planes.append(rm_plane)
+    if torch_in:
+        idx = torch.as_tensor(order, device=dev)
+        planes = [(a if sorted_ else a.index_select(0, idx)).contiguous() for a in planes]
+        slon, slat = site_lon[site_order].contiguous(), site_lat[site_order].contiguous()
+        counts = torch.empty((n_site, n_groups, n_bin), dtype=torch.int32, device=dev)
+        smax = torch.empty((n_site, max(n_trk, 1)), dtype=torch.float64, device=dev) if return_max else None
+    else:
+        planes = [np.ascontiguousarray(a if sorted_ else a[order]) for a in planes]
+        slon, slat = np.ascontiguousarray(site_lon[site_order]), np.ascontiguousarray(site_lat[site_order])
+        counts = np.empty((n_site, n_groups, n_bin), dtype=np.int32)
+        smax = np.empty((n_site, max(n_trk, 1)), dtype=np.float64) if return_max else None
+    ptr = (lambda a: a.data_ptr()) if torch_in else (lambda a: a.ctypes.data)
+    trk = _lib.WindTracks(n_trk=n_trk, n_t=n_t, row_stride=n_t, lon=ptr(planes[0]), lat=ptr(planes[1]), v=ptr(planes[2]),
+                          u250=ptr(planes[3]), v250=ptr(planes[4]), u850=ptr(planes[5]), v850=ptr(planes[6]),
+                          rmax_km=ptr(planes[7]) if rm_plane is not None else None,
+                          n_group=n_groups, group_off=group_off.ctypes.data_as(C.POINTER(C.c_int64)))
+    prm = _lib.WindParams(dt_s=dt_s, ck_cd=ck_cd, r_out_km=r_out_km, rmax_const_km=rm_const, substeps=substeps)
+    ctx = _Context(engine, device)
+    try:
+        args = (ctx.h, C.byref(trk), C.byref(prm), n_site, ptr(slon), ptr(slat), n_bin, thr.ctypes.data_as(_lib.DP), ptr(counts),
+                ptr(smax) if smax is not None else None)
+        if torch_in:
+            ctx.check(ctx.L.tcr_windfield_dev(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        else:
+            ctx.check(ctx.L.tcr_windfield_host(*args))
+    finally:
+        if torch_in and ctx.own:
+            torch.cuda.current_stream(dev).synchronize()       # the context's workspaces go with it
+        ctx.close()
+
+    # back to the caller's site and storm order
+    if torch_in:
+        out_counts = torch.empty_like(counts)
+        out_counts[site_order] = counts
+        res = dict(counts=out_counts, thresholds=thr)
+        if return_max:
+            m = smax[:, :n_trk]
+            out = torch.empty_like(m)
+            out[site_order] = m
+            if not sorted_:
+                un = torch.empty_like(out)
+                un[:, idx] = out
+                out = un
+            res['site_max'] = out
+    else:
+        out_counts = np.empty_like(counts)
+        out_counts[site_order] = counts
+        res = dict(counts=out_counts, thresholds=thr)
+        if return_max:
+            out = np.empty((n_site, n_trk))
+            out[np.ix_(site_order, order)] = smax[:, :n_trk]
+            res['site_max'] = out
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------------------- CLI
+ENV_VARS = ('u250_trks', 'v250_trks', 'u850_trks', 'v850_trks')
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog='python -m tropical_cyclone_risk_amd.windfield',
+                                description='Wind-footprint exceedance counts and return periods of track files at sites.')
+    p.add_argument('tracks', nargs='+', help='track files (ensemble members); every year of every file is one group')
+    p.add_argument('--site', type=hazard._site, action='append', default=[], metavar='LON,LAT',
+                   help='repeatable; write --site=LON,LAT when LON is negative')
+    p.add_argument('--sites', metavar='FILE.csv', help='one LON,LAT per line (lines that are not two numbers are skipped)')
+    p.add_argument('--grid', type=hazard._grid, metavar='LON0:LON1:DLON,LAT0:LAT1:DLAT')
+    p.add_argument('--rmax-km', type=float, default=None, help='constant radius of maximum wind (default: Willoughby et al. 2006)')
+    p.add_argument('--r-out-km', type=float, default=500.0)
+    p.add_argument('--substeps', type=int, default=1, help='evaluation points per sample interval (1 = the samples only)')
+    p.add_argument('--ck-cd', type=float, default=None, help='Ck / Cd of the profile (default: the namelist\'s)')
+    p.add_argument('--thresholds', type=lambda t: hazard._range(t, '--thresholds'), default=hazard.DEFAULT_THRESHOLDS,
+                   metavar='LO:HI:STEP')
+    p.add_argument('--out', default='wind.npz')
+    p.add_argument('--device', type=int, default=0)
+    a = p.parse_args(argv)
+    if not (a.site or a.sites or a.grid):
+        p.error('give sites with --site, --sites or --grid')
+    return a
+
+
+def main(argv=None):
+    from .climatology import sample_spacing
+    args = parse_args(argv)
+    site_lon, site_lat = hazard.collect_sites(args)
+    if site_lon.size == 0:
+        raise SystemExit('no sites')
+    lon, lat, vmax, groups, gfile, gyear, more = hazard.load_groups(args.tracks, extra=('v_trks',) + ENV_VARS + ('time',))
+    total_years = len(gfile)
+    dt = sample_spacing(more['time'])
+    v, *env = (np.concatenate([np.asarray(a, dtype=np.float64) for a in more[k]]) for k in ('v_trks',) + ENV_VARS)
+    res = site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt, rmax_km=args.rmax_km, ck_cd=args.ck_cd,
+                    r_out_km=args.r_out_km, substeps=args.substeps, thresholds=args.thresholds, device=args.device,
+                    n_groups=total_years)
+    rp = hazard.return_periods(res['counts'], total_years)
+    np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,
+             total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps,
+             rmax_km=np.nan if args.rmax_km is None else args.rmax_km, dt_s=dt, group_file=gfile, group_year=gyear,
+             files=np.array([str(f) for f in args.tracks]))
+    print('%d sites, %d storms, %d groups (%d files), total_years = %d, r_out = %g km, %d substeps -> %s'
+          % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.r_out_km, args.substeps, args.out))
+    if site_lon.size <= 10:
+        print('return period (years) by threshold (m/s): ' + ' '.join('%6g' % t for t in res['thresholds']))
+        for i in range(site_lon.size):
+            print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%6.3g' % x for x in rp[i]))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
