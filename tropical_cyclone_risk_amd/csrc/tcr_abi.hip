@@ -129,6 +129,24 @@ struct CopyPool {
 
 }  // namespace
 
+// Workspace of one site-scan analysis (tcr_sitescan.h).  d: records, caps, record counts, partial counts, chunk table + pair counter,
+// the prep kernel's own; h: the pinned staging of the chunk table.
+struct ScanWs {
+    void *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t cap[6] = {0, 0, 0, 0, 0, 0};
+    int64_t *h = nullptr;
+    size_t h_cap = 0;
+    hipEvent_t ev = nullptr, done = nullptr;        // chunk table uploaded / last call done
+    unsigned long long *pairs = nullptr;            // pairs the last call evaluated (inside d[4])
+    void release()
+    {
+        for (void *p : d) (void)hipFree(p);
+        if (h) (void)hipHostFree(h);
+        if (ev) (void)hipEventDestroy(ev);
+        if (done) (void)hipEventDestroy(done);
+    }
+};
+
 struct tcr_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -215,13 +233,9 @@ struct tcr_ctx {
     std::vector<hipEvent_t> st_pool;
     std::vector<int> st_id;
     size_t st_used = 0;
-    // site hazard (tcr_hazard.hip): samples, caps, live counts, partial counts, chunk table; the pinned staging of the chunk table
-    void *d_hz[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t hz_cap[5] = {0, 0, 0, 0, 0};
-    int64_t *hz_h = nullptr;
-    size_t hz_h_cap = 0;
-    hipEvent_t hz_ev = nullptr, hz_done = nullptr;  // chunk table uploaded / last call done
-    unsigned long long *hz_pairs = nullptr;         // pairs the last call evaluated (inside d_hz[4])
+    // site hazard (tcr_hazard.hip) and wind footprint (tcr_windfield.hip): a workspace each, so that one call of either may be in
+    // flight on streams of their own
+    ScanWs hz, wf;
     // landfall (tcr_landfall.hip): node coordinates (lon, then lat) and land bit plane of the uploaded grid
     double *lf_xy = nullptr;
     uint32_t *lf_bits = nullptr;
@@ -231,14 +245,6 @@ struct tcr_ctx {
     // track climatology (tcr_climatology.hip): key workspace of tracks longer than the kernel's LDS slice
     void *d_cl = nullptr;
     size_t cl_cap = 0;
-    // wind footprint (tcr_windfield.hip): records, caps, record counts, partial counts, chunk table, staged samples; the pinned
-    // staging of the chunk table
-    void *d_wf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t wf_cap[6] = {0, 0, 0, 0, 0, 0};
-    int64_t *wf_h = nullptr;
-    size_t wf_h_cap = 0;
-    hipEvent_t wf_ev = nullptr, wf_done = nullptr;  // chunk table uploaded / last call done
-    unsigned long long *wf_pairs = nullptr;         // pairs the last call evaluated (inside d_wf[4])
 };
 
 namespace {
@@ -1100,16 +1106,9 @@ int tcr_ctx_destroy(tcr_ctx *ctx)
     for (auto &ev : ctx->st_pool) if (ev) (void)hipEventDestroy(ev);
     for (auto &g : ctx->graphs) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); }
     (void)hipFree(ctx->d_round_key);
-    for (void *p : ctx->d_hz) (void)hipFree(p);
-    if (ctx->hz_h) (void)hipHostFree(ctx->hz_h);
-    if (ctx->hz_ev) (void)hipEventDestroy(ctx->hz_ev);
-    if (ctx->hz_done) (void)hipEventDestroy(ctx->hz_done);
+    ctx->hz.release(); ctx->wf.release();
     (void)hipFree(ctx->lf_xy); (void)hipFree(ctx->lf_bits);
     (void)hipFree(ctx->d_cl);
-    for (void *p : ctx->d_wf) (void)hipFree(p);
-    if (ctx->wf_h) (void)hipHostFree(ctx->wf_h);
-    if (ctx->wf_ev) (void)hipEventDestroy(ctx->wf_ev);
-    if (ctx->wf_done) (void)hipEventDestroy(ctx->wf_done);
     for (int i = 0; i < 2; ++i) { if (ctx->h_stage[i]) (void)hipHostFree(ctx->h_stage[i]); if (ctx->h_stage_ev[i]) (void)hipEventDestroy(ctx->h_stage_ev[i]); }
     (void)hipFree(ctx->d_hist_partial); (void)hipFree(ctx->d_cell); (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_tc_idx); (void)hipFree(ctx->d_tc_count); (void)hipFree(ctx->d_queue); (void)hipFree(ctx->d_sidx); (void)hipFree(ctx->d_park[0]); (void)hipFree(ctx->d_park[1]); (void)hipFree(ctx->d_sc_table); (void)hipFree(ctx->d_pf); (void)hipFree(ctx->d_screen_skip); (void)hipFree(ctx->d_und_list); (void)hipFree(ctx->d_und_count); (void)hipFree(ctx->d_tab);
     (void)hipStreamDestroy(ctx->stream);
@@ -2339,6 +2338,7 @@ int tcr_round_graph_stats(tcr_ctx *ctx, int64_t *n_graphs, int64_t *n_replays)
 }  // extern "C"
 
 #include "tcr_comm.hip"                  // multi-GPU exchange (RCCL, loaded at run time)
+#include "tcr_sitescan.h"                // what the two per-site analyses share: tile scan, culling caps, chunk table, workspaces
 #include "tcr_hazard.hip"                // site wind hazard (near-site intensity, exceedance counts)
 #include "tcr_landfall.hip"              // landfall detection (sea -> land steps of the model's land decision)
 #include "tcr_climatology.hip"           // track climatology (track, exceedance, genesis, LMI density and PDI per cell)

@@ -1,0 +1,357 @@
+// The site scan: what the per-site analyses of a track ensemble (tcr_hazard.hip, tcr_windfield.hip) share.  Each of them turns
+// every storm into a row of wave-uniform records, and wants
+//
+//   site_max[site][storm] = max of value(site, record) over the storm's records with haversine(site, record) <= R   (NaN: none)
+//   counts[site][group][bin] = #storms of the group with site_max >= thr[bin]
+//
+// An analysis supplies
+//   a record type   plain doubles that begin with the half-angle terms { sp, cp, sl, cl, cosp } of the point (the distance test),
+//                   with  static Rec uniform(const Rec *)  (the terms a pair reads, through scalar loads)  and
+//                   void centre(HzCap *) const  (the unit vector of the point, for a cap centred on it);
+//   a prep kernel   one wave per storm: writes the storm's records to the front of its row and ends with scan_finish_row
+//                   (NaN padding of the last segment, record count, bounding caps of the storm and of every kHzSeg-record segment);
+//   a policy        { Rec, kUnroll, value(site, record, a) }: a compile-time type that travels to the kernel by value, so that it
+//                   can carry launch-uniform parameters.  Nothing here branches at run time on which analysis is running.
+// and calls scan_run with a workspace of its own (ScanWs, two instances in tcr_ctx: a hazard call and a footprint call may be in
+// flight on different streams of one context).
+//
+//   k_site_scan      one wave per (tile of 64 sites, chunk of storms of one group): every lane holds one site's terms in registers;
+//                    the records are wave-uniform and come through scalar loads.  A storm or segment whose cap is farther than R
+//                    (plus both radii) from the tile's cap is skipped without touching its records;
+//   k_hazard_reduce  sums the integer per-chunk partial counts of each group.
+//
+// Culling is conservative: caps are padded by kHzPad radians and the test keeps a margin of kHzDotPad in cosine space (both far above
+// the rounding of the cap arithmetic), so a skipped pair is always farther than R.  It changes which pairs are evaluated, never a
+// result: a pair's value does not depend on the other pairs, max and integer sums do not depend on order, so results are
+// bit-identical whatever the launch shape.
+
+namespace {
+
+constexpr int kHzSeg = 32;                  // records per culling segment
+constexpr int kHzMaxBin = 64;
+constexpr double kHzPad = 1e-9;             // radians added to every cap radius
+constexpr double kHzDotPad = 1e-12;         // cosine-space margin of the cap test
+
+struct HzCap { double x, y, z, cr, sr, r, pad0, pad1; };           // cap: centre, cos / sin of radius, radius (64 bytes)
+
+// what a prep kernel writes and the scan reads
+template <class Rec>
+struct ScanRows {
+    Rec *rec;                               // [n_trk][n_seg_max * kHzSeg]
+    HzCap *seg;                             // [n_trk][n_seg_max]
+    HzCap *storm;                           // [n_trk]
+    int32_t *cnt;                           // [n_trk] records
+    int64_t n_seg_max;
+};
+
+// one site's terms: half angles (distance), full angles (direction); a policy's value() reads what it needs, the rest is dead code
+struct ScanSite { double sp, cp, sl, cl, cosp, sinp, sinl, cosl; };
+
+template <class Rec>
+struct ScanArgs {
+    ScanRows<Rec> rows;
+    const int64_t *chunks;                  // [n_chunk][3]: storm begin, storm end, group
+    const double *site_lon, *site_lat;
+    int64_t n_site, n_tile, n_trk;
+    double a_R, r_ang;                      // a threshold of R, R in radians
+    int32_t n_bin;
+    double thr[kHzMaxBin];
+    int32_t *part;                          // [n_chunk][n_site][n_bin]
+    double *site_max;                       // [n_site][n_trk] or NULL
+    unsigned long long *pairs;              // pairs evaluated (after culling)
+};
+
+// Wave-uniform reads of data no kernel here writes while it runs: through the constant address space, so that the compiler issues
+// scalar loads (the values then feed the fp64 VALU as SGPR operands) instead of vector loads of one address per lane.
+template <typename T>
+__device__ __forceinline__ T hz_uniform(const T *p) { return *(const __attribute__((address_space(4))) T *)p; }
+__device__ __forceinline__ HzCap hz_uniform(const HzCap *p)
+{
+    const double *d = &p->x;
+    return HzCap{hz_uniform(d), hz_uniform(d + 1), hz_uniform(d + 2), hz_uniform(d + 3), hz_uniform(d + 4), hz_uniform(d + 5), 0.0, 0.0};
+}
+
+__device__ __forceinline__ double hz_a(double sp1, double cp1, double sl1, double cl1, double cosp1,
+                                       double sp2, double cp2, double sl2, double cl2, double cosp2)
+{
+    const double t1 = sp1 * cp2 - cp1 * sp2;     // sin((phi1 - phi2) / 2)
+    const double t2 = sl1 * cl2 - cl1 * sl2;     // sin((lam1 - lam2) / 2)
+    return t1 * t1 + (cosp1 * cosp2) * (t2 * t2);
+}
+
+__device__ __forceinline__ double hz_angle(double a) { return 2.0 * asin(sqrt(fmin(fmax(a, 0.0), 1.0))); }
+
+__device__ __forceinline__ double wave_max(double x)
+{
+    for (int o = 32; o >= 1; o >>= 1) x = fmax(x, __shfl_xor(x, o, 64));
+    return x;
+}
+
+// cap (centre = the record at `mid`, radius = the largest angle from it) of the records [b, e) of one row
+template <class Rec>
+__device__ void hz_cap(const Rec *row, int b, int e, HzCap *out)
+{
+    const int lane = threadIdx.x;
+    const Rec &c = row[b + (e - b) / 2];
+    double r = 0.0;
+    for (int j = b + lane; j < e; j += 64) {
+        const Rec &p = row[j];
+        r = fmax(r, hz_angle(hz_a(c.sp, c.cp, c.sl, c.cl, c.cosp, p.sp, p.cp, p.sl, p.cl, p.cosp)));
+    }
+    r = wave_max(r) + kHzPad;
+    if (lane == 0) {
+        c.centre(out);
+        out->cr = cos(r); out->sr = sin(r); out->r = r; out->pad0 = out->pad1 = 0.0;
+    }
+}
+
+// the end of a prep kernel, whose lanes have written the n records of storm s to the front of its row
+template <class Rec>
+__device__ void scan_finish_row(const ScanRows<Rec> &o, int64_t s, int n)
+{
+    const int lane = threadIdx.x;
+    Rec *row = o.rec + s * o.n_seg_max * kHzSeg;
+    // the rest of the last segment: records no distance test passes (NaN terms), so that every segment is kHzSeg records long
+    Rec pad;
+    for (size_t i = 0; i < sizeof(Rec) / sizeof(double); ++i) reinterpret_cast<double *>(&pad)[i] = NAN;
+    for (int j = n + lane; j < (n + kHzSeg - 1) / kHzSeg * kHzSeg; j += 64) row[j] = pad;
+    __syncthreads();                                    // the caps read records other lanes wrote
+    if (lane == 0) o.cnt[s] = n;
+    if (n == 0) return;
+    hz_cap(row, 0, n, o.storm + s);
+    for (int k = 0; k * kHzSeg < n; ++k) hz_cap(row, k * kHzSeg, min(n, (k + 1) * kHzSeg), o.seg + s * o.n_seg_max + k);
+}
+
+// true when no point of the cap can be within the tile's padded radius (cos_t, sin_t, r_t) of the tile centre (tx, ty, tz)
+__device__ __forceinline__ bool hz_far(const HzCap &c, double tx, double ty, double tz, double ct, double st, double rt)
+{
+    if (c.r + rt >= kPi) return false;
+    const double dot = c.x * tx + c.y * ty + c.z * tz;
+    return dot < c.cr * ct - c.sr * st - kHzDotPad;     // angle(centres) > r_cap + r_tile
+}
+
+template <class Policy>
+__global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec> a, Policy pol)
+{
+    using Rec = typename Policy::Rec;
+    extern __shared__ int32_t hist[];                   // [n_bin + 1][64]: storms of this lane whose max passes exactly k thresholds
+    const int lane = threadIdx.x;
+    const int64_t tile = blockIdx.x % a.n_tile, chunk = blockIdx.x / a.n_tile;
+    const int64_t site = tile * 64 + lane;
+    const bool valid = site < a.n_site;
+    const int64_t site0 = tile * 64;
+    const int64_t my = valid ? site : site0;
+    const double y = a.site_lat[my], x = a.site_lon[my];
+    const double hp = y * (kPi / 360.0), hl = x * (kPi / 360.0), phi = y * (kPi / 180.0), lam = x * (kPi / 180.0);
+    const ScanSite me{sin(hp), cos(hp), sin(hl), cos(hl), cos(phi), sin(phi), sin(lam), cos(lam)};
+    for (int k = 0; k <= a.n_bin; ++k) hist[k * 64 + lane] = 0;
+
+    // tile cap: centre = the tile's first site, radius = the largest angle from it, padded by R
+    const double sp0 = __shfl(me.sp, 0, 64), cp0 = __shfl(me.cp, 0, 64), sl0 = __shfl(me.sl, 0, 64), cl0 = __shfl(me.cl, 0, 64);
+    const double cosp0 = __shfl(me.cosp, 0, 64);
+    const double rt = wave_max(hz_angle(hz_a(sp0, cp0, sl0, cl0, cosp0, me.sp, me.cp, me.sl, me.cl, me.cosp))) + kHzPad + a.r_ang + kHzPad;
+    const double phi0 = __shfl(y, 0, 64) * (kPi / 180.0), lam0 = __shfl(x, 0, 64) * (kPi / 180.0);
+    const double tx = cos(phi0) * cos(lam0), ty = cos(phi0) * sin(lam0), tz = sin(phi0);
+    const double ct = cos(rt), st = sin(rt);
+
+    const int64_t s_begin = hz_uniform(a.chunks + 3 * chunk), s_end = hz_uniform(a.chunks + 3 * chunk + 1);
+    const unsigned long long n_lanes = (unsigned long long)min<int64_t>(64, a.n_site - site0);
+    unsigned long long pairs = 0;
+    __syncthreads();
+    for (int64_t s = s_begin; s < s_end; ++s) {
+        double m = NAN;
+        const int n = hz_uniform(a.rows.cnt + s);
+        if (n > 0 && !hz_far(hz_uniform(a.rows.storm + s), tx, ty, tz, ct, st, rt)) {
+            const Rec *row = a.rows.rec + s * a.rows.n_seg_max * kHzSeg;
+            const HzCap *segs = a.rows.seg + s * a.rows.n_seg_max;
+            for (int k = 0; k * kHzSeg < n; ++k) {
+                if (hz_far(hz_uniform(segs + k), tx, ty, tz, ct, st, rt)) continue;
+                pairs += (unsigned long long)(min(n, (k + 1) * kHzSeg) - k * kHzSeg);
+                const Rec *seg = row + k * kHzSeg;
+#pragma unroll Policy::kUnroll
+                for (int j = 0; j < kHzSeg; ++j) {                  // (padding records fail the test: NaN terms)
+                    const Rec p = Rec::uniform(seg + j);
+                    const double q = hz_a(me.sp, me.cp, me.sl, me.cl, me.cosp, p.sp, p.cp, p.sl, p.cl, p.cosp);
+                    if (q <= a.a_R) m = fmax(m, pol.value(me, p, q));   // fmax skips NaN: the start, or a NaN value
+                }
+            }
+        }
+        if (a.site_max && valid) a.site_max[site * a.n_trk + s] = m;
+        if (!isnan(m)) {
+            int lo = 0, hi = a.n_bin;                   // k = #thresholds <= m
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (a.thr[mid] <= m) lo = mid + 1; else hi = mid; }
+            hist[lo * 64 + lane] += 1;
+        }
+    }
+    if (valid) {
+        int32_t c = 0;
+        int32_t *out = a.part + (chunk * a.n_site + site) * a.n_bin;
+        for (int b = a.n_bin - 1; b >= 0; --b) { c += hist[(b + 1) * 64 + lane]; out[b] = c; }
+    }
+    if (lane == 0 && pairs) atomicAdd(a.pairs, pairs * n_lanes);
+}
+
+// counts[site][g][b] = sum of the partials of the chunks of group g
+__global__ __launch_bounds__(256) void k_hazard_reduce(const int32_t *__restrict__ part, const int64_t *__restrict__ gch_off,
+                                                       int64_t n_site, int32_t n_group, int32_t n_bin, int32_t *__restrict__ counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_site * n_group * n_bin) return;
+    const int64_t b = i % n_bin, g = (i / n_bin) % n_group, site = i / ((int64_t)n_bin * n_group);
+    int32_t c = 0;
+    for (int64_t k = gch_off[g]; k < gch_off[g + 1]; ++k) c += part[(k * n_site + site) * n_bin + b];
+    counts[i] = c;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host
+// ScanWs::d: 0 records, 1 caps (storms, then segments), 2 record counts, 3 partial counts, 4 chunk table + pair counter,
+// 5 the prep kernel's own workspace
+template <typename T>
+int scan_grow(tcr_ctx *ctx, ScanWs &w, int i, size_t count)
+{
+    if (w.cap[i] >= count * sizeof(T)) return 0;
+    (void)hipFree(w.d[i]);
+    w.d[i] = nullptr; w.cap[i] = 0;
+    T *p = nullptr;
+    if (dev_alloc(ctx, &p, count)) return -1;
+    w.d[i] = p; w.cap[i] = count * sizeof(T);
+    return 0;
+}
+
+// the arguments every analysis has; `who` is the entry point's prefix ("tcr_hazard"), n_t_rule its bound on n_t in words
+template <class Tracks>
+int scan_check(tcr_ctx *ctx, const char *who, const Tracks *t, int64_t n_t_max, const char *n_t_rule, int64_t n_site, int32_t n_bin,
+               const double *thr)
+{
+    if (n_bin < 1 || n_bin > kHzMaxBin) return fail(ctx, "%s: n_bin must be in [1, 64]", who);
+    for (int b = 0; b < n_bin; ++b)
+        if (!std::isfinite(thr[b]) || (b > 0 && !(thr[b] > thr[b - 1]))) return fail(ctx, "%s: thresholds must be finite and ascending", who);
+    if (n_site < 1 || t->n_trk < 0 || t->n_t < 1 || t->n_t > n_t_max || t->row_stride < t->n_t || t->n_group < 1)
+        return fail(ctx, "%s: bad sizes (n_site >= 1, %s, row_stride >= n_t, n_group >= 1)", who, n_t_rule);
+    if (t->group_off[0] != 0 || t->group_off[t->n_group] != t->n_trk) return fail(ctx, "%s: group_off must run from 0 to n_trk", who);
+    for (int32_t g = 0; g < t->n_group; ++g)
+        if (t->group_off[g + 1] < t->group_off[g]) return fail(ctx, "%s: group_off must not decrease", who);
+    return 0;
+}
+
+// One call on stream st: chunk table, workspaces, launch, reduction.  launch(args, workspace 5, grid, LDS bytes) enqueues the
+// analysis's prep kernel, then its k_site_scan instantiation, and returns the first launch error.  n_rec: the most records a
+// storm can have; radius_km on a sphere of re_km; extra_bytes: what the prep kernel wants in workspace 5.
+template <class Rec, class Tracks, class Launch>
+int scan_run(tcr_ctx *ctx, ScanWs &w, const char *who, const Tracks *t, int64_t n_rec, size_t extra_bytes, int64_t n_site,
+             const double *site_lon, const double *site_lat, double radius_km, double re_km, int32_t n_bin, const double *thresholds,
+             int32_t *counts, double *site_max, hipStream_t st, Launch launch)
+{
+    const int64_t n_trk = t->n_trk, n_group = t->n_group;
+    const int64_t n_tile = (n_site + 63) / 64, n_seg_max = (n_rec + kHzSeg - 1) / kHzSeg;
+
+    // chunks: every group split into pieces of at most `ch` storms, sized so that the grid has ~8192 waves
+    const int64_t want = std::max<int64_t>(1, (8192 + n_tile - 1) / n_tile);
+    const int64_t ch = std::max<int64_t>(16, (n_trk + want - 1) / want);
+    std::vector<int64_t> tab, gch(1, 0);
+    for (int64_t g = 0; g < n_group; ++g) {
+        for (int64_t b = t->group_off[g]; b < t->group_off[g + 1]; b += ch) {
+            tab.push_back(b); tab.push_back(std::min(b + ch, (int64_t)t->group_off[g + 1])); tab.push_back(g);
+        }
+        gch.push_back((int64_t)tab.size() / 3);
+    }
+    const int64_t n_chunk = (int64_t)tab.size() / 3;
+    if (n_tile * n_chunk >= ((int64_t)1 << 31) || n_site * n_group * n_bin >= ((int64_t)1 << 39))
+        return fail(ctx, "%s: too many sites x storm chunks for one launch; split the sites", who);
+    const size_t n_tab = tab.size() + gch.size();
+
+    if (scan_grow<Rec>(ctx, w, 0, (size_t)std::max<int64_t>(1, n_trk * n_seg_max * kHzSeg)) ||
+        scan_grow<HzCap>(ctx, w, 1, (size_t)std::max<int64_t>(1, n_trk * (n_seg_max + 1))) ||
+        scan_grow<int32_t>(ctx, w, 2, (size_t)std::max<int64_t>(1, n_trk)) ||
+        scan_grow<int32_t>(ctx, w, 3, (size_t)std::max<int64_t>(1, n_chunk * n_site * n_bin)) ||
+        scan_grow<int64_t>(ctx, w, 4, n_tab + 1) ||
+        (extra_bytes && scan_grow<char>(ctx, w, 5, extra_bytes)))
+        return -1;
+    // the chunk table goes up through a pinned buffer of the workspace; the previous call's upload must be done with it
+    if (w.ev) HIPCHK(ctx, hipEventSynchronize(w.ev));
+    else {
+        HIPCHK(ctx, hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+        HIPCHK(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+    }
+    if (w.h_cap < n_tab) {
+        if (w.h) (void)hipHostFree(w.h);
+        w.h = nullptr; w.h_cap = 0;
+        HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void **>(&w.h), n_tab * sizeof(int64_t)));
+        w.h_cap = n_tab;
+    }
+    memcpy(w.h, tab.data(), tab.size() * sizeof(int64_t));
+    memcpy(w.h + tab.size(), gch.data(), gch.size() * sizeof(int64_t));
+    int64_t *d_tab = static_cast<int64_t *>(w.d[4]);
+    unsigned long long *d_pairs = reinterpret_cast<unsigned long long *>(d_tab + n_tab);
+    HIPCHK(ctx, hipMemcpyAsync(d_tab, w.h, n_tab * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipEventRecord(w.ev, st));
+    HIPCHK(ctx, hipMemsetAsync(d_pairs, 0, sizeof(unsigned long long), st));
+    w.pairs = d_pairs;
+
+    HzCap *caps = static_cast<HzCap *>(w.d[1]);
+    int32_t *part = static_cast<int32_t *>(w.d[3]);
+    if (n_trk > 0) {                                    // (then every storm is in a chunk: n_chunk > 0)
+        ScanArgs<Rec> m{};
+        m.rows = ScanRows<Rec>{static_cast<Rec *>(w.d[0]), caps + n_trk, caps, static_cast<int32_t *>(w.d[2]), n_seg_max};
+        m.chunks = d_tab;
+        m.site_lon = site_lon; m.site_lat = site_lat;
+        m.n_site = n_site; m.n_tile = n_tile; m.n_trk = n_trk;
+        const double h = sin(radius_km / (2.0 * re_km));
+        m.a_R = h * h; m.r_ang = radius_km / re_km;
+        m.n_bin = n_bin;
+        for (int b = 0; b < n_bin; ++b) m.thr[b] = thresholds[b];
+        m.part = part; m.site_max = site_max; m.pairs = d_pairs;
+        HIPCHK(ctx, launch(m, w.d[5], dim3((unsigned)(n_tile * n_chunk)), sizeof(int32_t) * 64 * (n_bin + 1)));
+    }
+    const int64_t n_out = n_site * n_group * n_bin;
+    hipLaunchKernelGGL(k_hazard_reduce, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, part, d_tab + tab.size(), n_site,
+                       (int32_t)n_group, n_bin, counts);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(w.done, st));
+    return 0;
+}
+
+// the sites and outputs of a _host entry point on the device (buffers of B), and the way back
+struct ScanHostIO {
+    const double *site_lon, *site_lat;
+    int32_t *counts;
+    double *site_max;
+    size_t n_out, n_max;
+    bool ok;
+};
+
+template <class Tracks>
+ScanHostIO scan_host_io(DevBuf &B, const Tracks *t, int64_t n_site, const double *site_lon, const double *site_lat, int32_t n_bin,
+                        bool want_max)
+{
+    ScanHostIO d{};
+    d.site_lon = B.put(site_lon, (size_t)n_site); d.site_lat = B.put(site_lat, (size_t)n_site);
+    d.n_out = (size_t)n_site * t->n_group * n_bin; d.n_max = (size_t)n_site * t->n_trk;
+    d.counts = B.get<int32_t>(d.n_out);
+    d.site_max = want_max ? B.get<double>((size_t)n_site * std::max<int64_t>(1, t->n_trk)) : nullptr;
+    d.ok = d.site_lon && d.site_lat && d.counts && (!want_max || d.site_max);
+    return d;
+}
+
+int scan_download(tcr_ctx *ctx, const ScanHostIO &d, int32_t *counts, double *site_max)
+{
+    HIPCHK(ctx, hipMemcpyAsync(counts, d.counts, sizeof(int32_t) * d.n_out, hipMemcpyDeviceToHost, ctx->stream));
+    if (site_max) HIPCHK(ctx, hipMemcpyAsync(site_max, d.site_max, sizeof(double) * d.n_max, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// pairs the last call on w evaluated; `who` as in scan_check
+int scan_pairs(tcr_ctx *ctx, const ScanWs &w, const char *who, int64_t *pairs)
+{
+    if (!pairs) return fail(ctx, "%s_pairs: NULL argument", who);
+    if (!w.pairs) return fail(ctx, "%s_pairs: no %s_* call on this context yet", who, who);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    unsigned long long v = 0;
+    HIPCHK(ctx, hipEventSynchronize(w.done));
+    HIPCHK(ctx, copy_sync(ctx->stream, &v, w.pairs, sizeof v, hipMemcpyDeviceToHost));
+    *pairs = (int64_t)v;
+    return 0;
+}
+
+}  // namespace

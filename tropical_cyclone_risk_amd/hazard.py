@@ -67,37 +67,42 @@ class _Context:
             self.h = None
 
 
-def site_hazard(lon, lat, vmax, groups, site_lon, site_lat, radius_km=100., thresholds=DEFAULT_THRESHOLDS, return_max=False,
-                engine=None, device=0, n_groups=None):
-    """Near-site intensity and exceedance counts of every site.
+def _as_planes(arrays, names):
+    """The track planes as fp64 arrays of the type and on the device of the first: (planes, conv), conv being the conversion."""
+    first = arrays[0]
+    if _is_tensor(first):
+        import torch
+        conv = lambda a: torch.as_tensor(a, dtype=torch.float64, device=first.device)     # noqa: E731
+    else:
+        conv = lambda a: np.asarray(a.cpu() if _is_tensor(a) else a, dtype=np.float64)    # noqa: E731
+    planes = [conv(a) for a in arrays]
+    if planes[0].ndim != 2 or any(tuple(p.shape) != tuple(planes[0].shape) for p in planes):
+        raise ValueError('%s must be [n_trk][n_t] arrays of one shape' % names)
+    return planes, conv
 
-    lon, lat, vmax: [n_trk][n_t] fp64 (the track file's lon_trks, lat_trks, vmax_trks; NaN past a track's end), NumPy arrays or
-    torch tensors on the GPU (then everything stays there).  groups: [n_trk] integer group of every storm, in [0, n_groups)
-    (default n_groups = max + 1; a group without storms counts 0).  site_lon / site_lat: [n_site], either longitude convention.
-    Returns a dict: ``counts`` [n_site][n_groups][n_bin] int32 (storms of the group whose near-site maximum is >= the threshold),
-    ``thresholds``, and with ``return_max`` ``site_max`` [n_site][n_trk] (NaN: no sample within the radius).  Arrays come back
-    in the type and on the device of ``lon``.  ``engine``: a TCEngine whose context is used (None: one is opened for the call).
-    """
-    torch_in = _is_tensor(lon)
+
+def _site_scan(entry, planes, conv, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device, make_args):
+    """What the per-site analyses (csrc/tcr_sitescan.h) share in front of the library: checks the sites and groups, puts the
+    storms of a group next to each other and the sites in spatial order, runs ``entry + '_dev'`` (torch tensors, on the current
+    stream) or ``entry + '_host'`` (NumPy) and returns ``counts``, ``thresholds`` and with return_max ``site_max`` in the
+    caller's site and storm order.  planes, conv: of _as_planes.  make_args(tracks, sites, out) -> the entry point's arguments
+    after the context: tracks holds the fields every tracks struct has and ``planes``, the pointers of the permuted planes;
+    sites = (n_site, lon, lat) and out = (n_bin, thresholds, counts, site_max) are ready to pass on.  The library is not
+    touched before every check here has passed."""
+    torch_in = _is_tensor(planes[0])
     if torch_in:
         import torch
         xp = torch
-        dev = lon.device
-        lon, lat, vmax = (torch.as_tensor(a, dtype=torch.float64, device=dev) for a in (lon, lat, vmax))
-        site_lon, site_lat = (torch.as_tensor(a, dtype=torch.float64, device=dev).reshape(-1) for a in (site_lon, site_lat))
+        dev = planes[0].device
         device = dev.index if dev.index is not None else torch.cuda.current_device()
     else:
         xp = np
-        lon, lat, vmax = (np.asarray(a, dtype=np.float64) for a in (lon, lat, vmax))
-        site_lon, site_lat = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (site_lon, site_lat))
-    if lon.ndim != 2 or tuple(lat.shape) != tuple(lon.shape) or tuple(vmax.shape) != tuple(lon.shape):
-        raise ValueError('lon, lat and vmax must be [n_trk][n_t] arrays of one shape')
+    site_lon, site_lat = (conv(a).reshape(-1) for a in (site_lon, site_lat))
     if site_lon.shape[0] != site_lat.shape[0] or site_lon.shape[0] < 1:
         raise ValueError('site_lon and site_lat must be non-empty and of one length')
     if not bool(xp.isfinite(site_lon).all()) or not bool(xp.isfinite(site_lat).all()):
         raise ValueError('site coordinates must be finite')
-    n_trk, n_t = int(lon.shape[0]), int(lon.shape[1])
-    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    n_trk, n_t = int(planes[0].shape[0]), int(planes[0].shape[1])
     g = np.asarray(groups.cpu() if _is_tensor(groups) else groups).reshape(-1)
     if g.shape[0] != n_trk or (n_trk and (g.dtype.kind not in 'iu' or g.min() < 0)):
         raise ValueError('groups must hold one non-negative integer per storm')
@@ -115,55 +120,70 @@ def site_hazard(lon, lat, vmax, groups, site_lon, site_lat, radius_km=100., thre
     n_site, n_bin = int(site_lon.shape[0]), int(thr.shape[0])
     if torch_in:
         idx = torch.as_tensor(order, device=dev)
-        planes = [a if sorted_ else a.index_select(0, idx) for a in (lon, lat, vmax)]
-        planes = [a.contiguous() for a in planes]
+        planes = [(a if sorted_ else a.index_select(0, idx)).contiguous() for a in planes]
         slon, slat = site_lon[site_order].contiguous(), site_lat[site_order].contiguous()
         counts = torch.empty((n_site, n_groups, max(n_bin, 1)), dtype=torch.int32, device=dev)
         smax = torch.empty((n_site, max(n_trk, 1)), dtype=torch.float64, device=dev) if return_max else None
     else:
-        planes = [np.ascontiguousarray(a if sorted_ else a[order]) for a in (lon, lat, vmax)]
+        planes = [np.ascontiguousarray(a if sorted_ else a[order]) for a in planes]
         slon, slat = np.ascontiguousarray(site_lon[site_order]), np.ascontiguousarray(site_lat[site_order])
         counts = np.empty((n_site, n_groups, max(n_bin, 1)), dtype=np.int32)
         smax = np.empty((n_site, max(n_trk, 1)), dtype=np.float64) if return_max else None
     ptr = (lambda a: a.data_ptr()) if torch_in else (lambda a: a.ctypes.data)
-    trk = _lib.HazardTracks(n_trk=n_trk, n_t=n_t, row_stride=n_t, lon=ptr(planes[0]), lat=ptr(planes[1]), vmax=ptr(planes[2]),
-                            n_group=n_groups, group_off=group_off.ctypes.data_as(C.POINTER(C.c_int64)))
+    tracks = dict(n_trk=n_trk, n_t=n_t, row_stride=n_t, n_group=n_groups, group_off=group_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                  planes=[ptr(a) for a in planes])
+    args = make_args(tracks, (n_site, ptr(slon), ptr(slat)),
+                     (n_bin, thr.ctypes.data_as(_lib.DP), ptr(counts), ptr(smax) if smax is not None else None))
     ctx = _Context(engine, device)
     try:
-        args = (ctx.h, C.byref(trk), n_site, ptr(slon), ptr(slat), float(radius_km), n_bin,
-                thr.ctypes.data_as(_lib.DP), ptr(counts), ptr(smax) if smax is not None else None)
         if torch_in:
-            ctx.check(ctx.L.tcr_hazard_dev(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            ctx.check(getattr(ctx.L, entry + '_dev')(ctx.h, *args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         else:
-            ctx.check(ctx.L.tcr_hazard_host(*args))
+            ctx.check(getattr(ctx.L, entry + '_host')(ctx.h, *args))
     finally:
         if torch_in and ctx.own:
             torch.cuda.current_stream(dev).synchronize()       # the context's workspaces go with it
         ctx.close()
 
     # back to the caller's site and storm order
-    if torch_in:
-        out_counts = torch.empty_like(counts)
-        out_counts[site_order] = counts
-        res = dict(counts=out_counts, thresholds=thr)
-        if return_max:
-            m = smax[:, :n_trk]
-            out = torch.empty_like(m)
-            out[site_order] = m
-            if not sorted_:
-                un = torch.empty_like(out)
-                un[:, idx] = out
-                out = un
-            res['site_max'] = out
-    else:
-        out_counts = np.empty_like(counts)
-        out_counts[site_order] = counts
-        res = dict(counts=out_counts, thresholds=thr)
-        if return_max:
-            out = np.empty((n_site, n_trk))
-            out[np.ix_(site_order, order)] = smax[:, :n_trk]
-            res['site_max'] = out
+    out_counts = xp.empty_like(counts)
+    out_counts[site_order] = counts
+    res = dict(counts=out_counts, thresholds=thr)
+    if return_max and torch_in:
+        m = smax[:, :n_trk]
+        out = torch.empty_like(m)
+        out[site_order] = m
+        if not sorted_:
+            un = torch.empty_like(out)
+            un[:, idx] = out
+            out = un
+        res['site_max'] = out
+    elif return_max:
+        out = np.empty((n_site, n_trk))
+        out[np.ix_(site_order, order)] = smax[:, :n_trk]
+        res['site_max'] = out
     return res
+
+
+def site_hazard(lon, lat, vmax, groups, site_lon, site_lat, radius_km=100., thresholds=DEFAULT_THRESHOLDS, return_max=False,
+                engine=None, device=0, n_groups=None):
+    """Near-site intensity and exceedance counts of every site.
+
+    lon, lat, vmax: [n_trk][n_t] fp64 (the track file's lon_trks, lat_trks, vmax_trks; NaN past a track's end), NumPy arrays or
+    torch tensors on the GPU (then everything stays there).  groups: [n_trk] integer group of every storm, in [0, n_groups)
+    (default n_groups = max + 1; a group without storms counts 0).  site_lon / site_lat: [n_site], either longitude convention.
+    Returns a dict: ``counts`` [n_site][n_groups][n_bin] int32 (storms of the group whose near-site maximum is >= the threshold),
+    ``thresholds``, and with ``return_max`` ``site_max`` [n_site][n_trk] (NaN: no sample within the radius).  Arrays come back
+    in the type and on the device of ``lon``.  ``engine``: a TCEngine whose context is used (None: one is opened for the call).
+    The library checks ``radius_km`` and ``thresholds`` (``_lib.TcrError``).
+    """
+    planes, conv = _as_planes((lon, lat, vmax), 'lon, lat and vmax')
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+
+    def make_args(tracks, sites, out):
+        lon_, lat_, vmax_ = tracks.pop('planes')
+        return (C.byref(_lib.HazardTracks(lon=lon_, lat=lat_, vmax=vmax_, **tracks)),) + sites + (float(radius_km),) + out
+    return _site_scan('tcr_hazard', planes, conv, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device, make_args)
 
 
 def return_periods(counts, total_years):

@@ -22,7 +22,7 @@ import sys
 import numpy as np
 
 from . import _lib, hazard
-from .hazard import _Context, _is_tensor
+from .hazard import _is_tensor
 
 MAX_SUBSTEPS = 64
 MAX_R_OUT_KM = 2000.0
@@ -59,29 +59,15 @@ def site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt_s, rmax_km=None, 
     ``thresholds``, and with ``return_max`` ``site_max`` [n_site][n_trk] (m/s; NaN: no sample within r_out_km), in the type and
     on the device of ``lon``.
     """
-    torch_in = _is_tensor(lon)
-    if torch_in:
-        import torch
-        xp = torch
-        dev = lon.device
-        conv = lambda a: torch.as_tensor(a, dtype=torch.float64, device=dev)     # noqa: E731
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-    else:
-        xp = np
-        conv = lambda a: np.asarray(a.cpu() if _is_tensor(a) else a, dtype=np.float64)   # noqa: E731
     if len(env) != 4:
         raise ValueError('env must be (u250, v250, u850, v850)')
-    planes = [conv(a) for a in (lon, lat, v) + tuple(env)]
-    site_lon, site_lat = (conv(a).reshape(-1) for a in (site_lon, site_lat))
-    if planes[0].ndim != 2 or any(tuple(p.shape) != tuple(planes[0].shape) for p in planes):
-        raise ValueError('lon, lat, v and the four env planes must be [n_trk][n_t] arrays of one shape')
+    planes, conv = hazard._as_planes((lon, lat, v) + tuple(env), 'lon, lat, v and the four env planes')
+    xp = np
+    if _is_tensor(planes[0]):
+        import torch as xp
     n_trk, n_t = int(planes[0].shape[0]), int(planes[0].shape[1])
     if n_t < 1:
         raise ValueError('the tracks need at least one sample')
-    if site_lon.shape[0] != site_lat.shape[0] or site_lon.shape[0] < 1:
-        raise ValueError('site_lon and site_lat must be non-empty and of one length')
-    if not bool(xp.isfinite(site_lon).all()) or not bool(xp.isfinite(site_lat).all()):
-        raise ValueError('site coordinates must be finite')
     dt_s = float(dt_s)
     if not (np.isfinite(dt_s) and dt_s > 0):
         raise ValueError('dt_s must be finite and > 0')
@@ -97,7 +83,7 @@ def site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt_s, rmax_km=None, 
     thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
     if not 1 <= thr.size <= 64 or not np.isfinite(thr).all() or np.any(np.diff(thr) <= 0):
         raise ValueError('thresholds must be 1 to 64 finite, strictly ascending values')
-    rm_const, rm_plane = 0.0, None
+    rm_const = 0.0
     if rmax_km is not None:
         if np.ndim(rmax_km.cpu() if _is_tensor(rmax_km) else rmax_km) == 0:
             rm_const = float(rmax_km)
@@ -108,83 +94,22 @@ def site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt_s, rmax_km=None, 
             if tuple(rm_plane.shape) != (n_trk, n_t):
                 raise ValueError('an rmax_km plane must be [n_trk][n_t]')
             n = _track_length(planes, xp)
-            ar = xp.arange(n_t, device=dev)[None, :] if torch_in else np.arange(n_t)[None, :]
+            ar = xp.arange(n_t, device=planes[0].device)[None, :] if xp is not np else np.arange(n_t)[None, :]
             used = (ar < n[:, None]) & (n[:, None] >= 2)
             ok = xp.isfinite(rm_plane) & (rm_plane > 0)
             if bool((used & ~ok).any()):
                 raise ValueError('rmax_km must be finite and > 0 at every sample of a track')
-    g = np.asarray(groups.cpu() if _is_tensor(groups) else groups).reshape(-1)
-    if g.shape[0] != n_trk or (n_trk and (g.dtype.kind not in 'iu' or g.min() < 0)):
-        raise ValueError('groups must hold one non-negative integer per storm')
-    g = g.astype(np.int64)
-    n_groups = int(n_groups if n_groups is not None else (g.max() + 1 if n_trk else 1))
-    if n_trk and g.max() >= n_groups:
-        raise ValueError('a group index is >= n_groups')
-    if n_groups < 1:
+            planes.append(rm_plane)
+    if n_groups is not None and int(n_groups) < 1:
         raise ValueError('n_groups must be >= 1')
-
-    # storms grouped contiguously (stable: storms keep their order inside a group), sites in spatial order
-    order = np.argsort(g, kind='stable')
-    group_off = np.zeros(n_groups + 1, dtype=np.int64)
-    group_off[1:] = np.cumsum(np.bincount(g, minlength=n_groups))
-    sorted_ = bool(np.all(order == np.arange(n_trk)))
-    site_order = hazard._spatial_order(site_lon, site_lat, xp)
-    n_site, n_bin = int(site_lon.shape[0]), int(thr.shape[0])
-    if rm_plane is not None:
-        planes.append(rm_plane)
-    if torch_in:
-        idx = torch.as_tensor(order, device=dev)
-        planes = [(a if sorted_ else a.index_select(0, idx)).contiguous() for a in planes]
-        slon, slat = site_lon[site_order].contiguous(), site_lat[site_order].contiguous()
-        counts = torch.empty((n_site, n_groups, n_bin), dtype=torch.int32, device=dev)
-        smax = torch.empty((n_site, max(n_trk, 1)), dtype=torch.float64, device=dev) if return_max else None
-    else:
-        planes = [np.ascontiguousarray(a if sorted_ else a[order]) for a in planes]
-        slon, slat = np.ascontiguousarray(site_lon[site_order]), np.ascontiguousarray(site_lat[site_order])
-        counts = np.empty((n_site, n_groups, n_bin), dtype=np.int32)
-        smax = np.empty((n_site, max(n_trk, 1)), dtype=np.float64) if return_max else None
-    ptr = (lambda a: a.data_ptr()) if torch_in else (lambda a: a.ctypes.data)
-    trk = _lib.WindTracks(n_trk=n_trk, n_t=n_t, row_stride=n_t, lon=ptr(planes[0]), lat=ptr(planes[1]), v=ptr(planes[2]),
-                          u250=ptr(planes[3]), v250=ptr(planes[4]), u850=ptr(planes[5]), v850=ptr(planes[6]),
-                          rmax_km=ptr(planes[7]) if rm_plane is not None else None,
-                          n_group=n_groups, group_off=group_off.ctypes.data_as(C.POINTER(C.c_int64)))
     prm = _lib.WindParams(dt_s=dt_s, ck_cd=ck_cd, r_out_km=r_out_km, rmax_const_km=rm_const, substeps=substeps)
-    ctx = _Context(engine, device)
-    try:
-        args = (ctx.h, C.byref(trk), C.byref(prm), n_site, ptr(slon), ptr(slat), n_bin, thr.ctypes.data_as(_lib.DP), ptr(counts),
-                ptr(smax) if smax is not None else None)
-        if torch_in:
-            ctx.check(ctx.L.tcr_windfield_dev(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        else:
-            ctx.check(ctx.L.tcr_windfield_host(*args))
-    finally:
-        if torch_in and ctx.own:
-            torch.cuda.current_stream(dev).synchronize()       # the context's workspaces go with it
-        ctx.close()
 
-    # back to the caller's site and storm order
-    if torch_in:
-        out_counts = torch.empty_like(counts)
-        out_counts[site_order] = counts
-        res = dict(counts=out_counts, thresholds=thr)
-        if return_max:
-            m = smax[:, :n_trk]
-            out = torch.empty_like(m)
-            out[site_order] = m
-            if not sorted_:
-                un = torch.empty_like(out)
-                un[:, idx] = out
-                out = un
-            res['site_max'] = out
-    else:
-        out_counts = np.empty_like(counts)
-        out_counts[site_order] = counts
-        res = dict(counts=out_counts, thresholds=thr)
-        if return_max:
-            out = np.empty((n_site, n_trk))
-            out[np.ix_(site_order, order)] = smax[:, :n_trk]
-            res['site_max'] = out
-    return res
+    def make_args(tracks, sites, out):
+        p = tracks.pop('planes') + [None]                  # (no rmax_km plane)
+        trk = _lib.WindTracks(lon=p[0], lat=p[1], v=p[2], u250=p[3], v250=p[4], u850=p[5], v850=p[6], rmax_km=p[7], **tracks)
+        return (C.byref(trk), C.byref(prm)) + sites + out
+    return hazard._site_scan('tcr_windfield', planes, conv, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device,
+                             make_args)
 
 
 # ---------------------------------------------------------------------------------------------------------------- CLI
