@@ -653,6 +653,40 @@ int tcr_windfield_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_wi
 /* (site, sample or sub-sample) pairs the last tcr_windfield_* call of this context evaluated after culling; waits for that call */
 int tcr_windfield_pairs(tcr_ctx *ctx, int64_t *pairs);
 
+/* ---- portfolio loss: event losses, year losses and loss-cost map of exposed values under the wind footprint -------- */
+/* replaces: nothing in the reference's code; puts a damage function on the wind footprint above and sums it over the sites inside
+ * the scan, so that the site_max[n_site][n_trk] matrix never exists.  The damage function is Emanuel (2011, "Global warming
+ * effects on U.S. hurricane damage", eq. 1), with the constants CLIMADA uses as its defaults (v_thresh = 25.7, v_half = 74.7 m/s).
+ *   m               site_max[i][s] of tcr_windfield_* for the same tracks, parameters and sites (NaN: no sample within r_out_km)
+ *   loss[i][s]      site_value[i] D,  D = x^3 / (1 + x^3),  x = max(m - v_thresh, 0) / (v_half_i - v_thresh);  0 when m is NaN.
+ *                   D(v_thresh) = 0, D(v_half) = 1/2, D -> 1.  v_half_i = site_v_half[i], or v_half when site_v_half is NULL.
+ *   event_loss      [n_trk]: sum over the sites of loss[i][s] (the event loss table)
+ *   year_agg        [n_group]: sum of event_loss over the storms of the group;  year_max [n_group]: their maximum.  Both 0 for a
+ *                   group without storms.
+ *   site_loss       [n_site]: sum over all storms of loss[i][s] (divided by the years: a loss-cost map)
+ *   counts          [n_site][n_group][n_bin] (int32): the footprint's exceedance counts, as tcr_windfield_* gives them
+ * Arguments: those of tcr_windfield_* under the same rules (their messages begin with "tcr_windfield:"), and v_thresh finite and
+ * >= 0, v_half finite and > v_thresh; site_value finite and >= 0 and site_v_half finite and > v_thresh at every site.
+ * tcr_loss_host checks the two site arrays; tcr_loss_dev cannot, and a site with a bad value or a bad v_half contributes 0 to
+ * every sum (its counts are still the footprint's).  No floating-point atomics: sites are summed per run of 64 consecutive sites
+ * by a fixed butterfly and the runs in ascending order, so event_loss[s] is bit-identical from run to run and does not depend on
+ * the other storms of the call or on their order; year_max likewise; year_agg depends on the storms of its group and their
+ * order, site_loss on the storm order and the group offsets.  Workspace: (n_site / 64) x n_trk doubles and one double per
+ * (site, chunk of storms), grown on demand; when it does not fit the call fails ("split the sites").  _dev: planes, sites,
+ * site_value, site_v_half and all outputs are device memory, asynchronous on `stream`; group_off and thresholds are host memory
+ * in both entry points.  The workspace is the context's third (next to the hazard's and the footprint's): calls of tcr_loss_* on
+ * one context must be ordered, but one may be in flight next to a tcr_windfield_* or tcr_hazard_* call on another stream. */
+typedef struct {
+    double v_thresh, v_half;
+} tcr_loss_params;
+int tcr_loss_dev(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_wind_params *wind, const tcr_loss_params *loss, int64_t n_site,
+                 const double *site_lon, const double *site_lat, const double *site_value, const double *site_v_half, int32_t n_bin,
+                 const double *thresholds, int32_t *counts, double *event_loss, double *year_agg, double *year_max, double *site_loss,
+                 void *stream);
+int tcr_loss_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_wind_params *wind, const tcr_loss_params *loss, int64_t n_site,
+                  const double *site_lon, const double *site_lat, const double *site_value, const double *site_v_half, int32_t n_bin,
+                  const double *thresholds, int32_t *counts, double *event_loss, double *year_agg, double *year_max, double *site_loss);
+
 #ifdef __cplusplus
 }
 #endif

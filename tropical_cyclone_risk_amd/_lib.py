@@ -38,7 +38,7 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_allgather_rows_dev', 'tcr_allgather_counts_dev', 'tcr_allreduce_sum_i64_dev', 'tcr_concat_rows_dev',
            'tcr_hazard_dev', 'tcr_hazard_host', 'tcr_hazard_pairs', 'tcr_land_upload', 'tcr_land_info', 'tcr_landfall_dev',
            'tcr_landfall_host', 'tcr_climatology_dev', 'tcr_climatology_host', 'tcr_windfield_dev', 'tcr_windfield_host',
-           'tcr_windfield_pairs')
+           'tcr_windfield_pairs', 'tcr_loss_dev', 'tcr_loss_host')
 TCR_COMM_ID_BYTES = 128
 
 
@@ -134,6 +134,11 @@ class WindParams(C.Structure):
     """tcr_wind_params: sample spacing, Ck / Cd, outer radius, constant rm (0: modelled) and sub-steps of tcr_windfield_*."""
     _fields_ = [('dt_s', C.c_double), ('ck_cd', C.c_double), ('r_out_km', C.c_double), ('rmax_const_km', C.c_double),
                 ('substeps', C.c_int32)]
+
+
+class LossParams(C.Structure):
+    """tcr_loss_params: threshold and (scalar) half-damage wind of the damage function of tcr_loss_*."""
+    _fields_ = [('v_thresh', C.c_double), ('v_half', C.c_double)]
 
 
 class TcrError(RuntimeError):
@@ -270,6 +275,9 @@ def lib():
                                     C.c_int32, DP, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tcr_windfield_host.argtypes = L.tcr_windfield_dev.argtypes[:-1]
     L.tcr_windfield_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.tcr_loss_dev.argtypes = [C.c_void_p, C.POINTER(WindTracks), C.POINTER(WindParams), C.POINTER(LossParams), C.c_int64] + \
+        [C.c_void_p] * 4 + [C.c_int32, DP] + [C.c_void_p] * 6
+    L.tcr_loss_host.argtypes = L.tcr_loss_dev.argtypes[:-1]
     if L.tcr_abi_version() != TCR_ABI_VERSION:
         raise TcrError('libtcrisk_hip.so ABI version %d != binding version %d'
                        % (L.tcr_abi_version(), TCR_ABI_VERSION))

@@ -11,6 +11,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -130,10 +131,10 @@ struct CopyPool {
 }  // namespace
 
 // Workspace of one site-scan analysis (tcr_sitescan.h).  d: records, caps, record counts, partial counts, chunk table + pair counter,
-// the prep kernel's own; h: the pinned staging of the chunk table.
+// the prep kernel's own, two of the analysis's own; h: the pinned staging of the chunk table.
 struct ScanWs {
-    void *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t cap[6] = {0, 0, 0, 0, 0, 0};
+    void *d[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t *h = nullptr;
     size_t h_cap = 0;
     hipEvent_t ev = nullptr, done = nullptr;        // chunk table uploaded / last call done
@@ -233,9 +234,9 @@ struct tcr_ctx {
     std::vector<hipEvent_t> st_pool;
     std::vector<int> st_id;
     size_t st_used = 0;
-    // site hazard (tcr_hazard.hip) and wind footprint (tcr_windfield.hip): a workspace each, so that one call of either may be in
-    // flight on streams of their own
-    ScanWs hz, wf;
+    // site hazard (tcr_hazard.hip), wind footprint (tcr_windfield.hip) and portfolio loss (tcr_loss.hip): a workspace each, so
+    // that one call of each may be in flight on streams of their own
+    ScanWs hz, wf, ls;
     // landfall (tcr_landfall.hip): node coordinates (lon, then lat) and land bit plane of the uploaded grid
     double *lf_xy = nullptr;
     uint32_t *lf_bits = nullptr;
@@ -1106,7 +1107,7 @@ int tcr_ctx_destroy(tcr_ctx *ctx)
     for (auto &ev : ctx->st_pool) if (ev) (void)hipEventDestroy(ev);
     for (auto &g : ctx->graphs) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); }
     (void)hipFree(ctx->d_round_key);
-    ctx->hz.release(); ctx->wf.release();
+    ctx->hz.release(); ctx->wf.release(); ctx->ls.release();
     (void)hipFree(ctx->lf_xy); (void)hipFree(ctx->lf_bits);
     (void)hipFree(ctx->d_cl);
     for (int i = 0; i < 2; ++i) { if (ctx->h_stage[i]) (void)hipHostFree(ctx->h_stage[i]); if (ctx->h_stage_ev[i]) (void)hipEventDestroy(ctx->h_stage_ev[i]); }
@@ -2343,3 +2344,4 @@ int tcr_round_graph_stats(tcr_ctx *ctx, int64_t *n_graphs, int64_t *n_replays)
 #include "tcr_landfall.hip"              // landfall detection (sea -> land steps of the model's land decision)
 #include "tcr_climatology.hip"           // track climatology (track, exceedance, genesis, LMI density and PDI per cell)
 #include "tcr_windfield.hip"             // wind footprint (peak wind at sites from a radial profile, exceedance counts)
+#include "tcr_loss.hip"                  // portfolio loss (damage function on the footprint, summed over sites inside the scan)

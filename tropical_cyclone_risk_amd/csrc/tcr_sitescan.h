@@ -12,6 +12,11 @@
 //                   (NaN padding of the last segment, record count, bounding caps of the storm and of every kHzSeg-record segment);
 //   a policy        { Rec, kUnroll, value(site, record, a) }: a compile-time type that travels to the kernel by value, so that it
 //                   can carry launch-uniform parameters.  Nothing here branches at run time on which analysis is running.
+//                   A policy with `static constexpr bool kLoss = true` (tcr_loss.hip) turns on the loss variant of the scan at
+//                   compile time: site_terms(site, valid) -> per-lane terms, loss(terms, m) -> the lane's loss of a storm, and
+//                   the buffers tile_loss [n_tile][n_trk] and site_part [n_chunk][n_site].  Per storm the wave sums its 64 lane
+//                   losses with a fixed butterfly and lane 0 stores the sum; every lane keeps a running sum of its own losses in
+//                   storm order.  Policies without kLoss compile to the code they had before the variant existed.
 // and calls scan_run with a workspace of its own (ScanWs, two instances in tcr_ctx: a hazard call and a footprint call may be in
 // flight on different streams of one context).
 //
@@ -87,6 +92,19 @@ __device__ __forceinline__ double wave_max(double x)
     return x;
 }
 
+// the same butterfly with +: a + b == b + a bit for bit, so every lane ends with the same sum, in an order fixed by the lane numbers
+__device__ __forceinline__ double wave_sum(double x)
+{
+    for (int o = 32; o >= 1; o >>= 1) x = x + __shfl_xor(x, o, 64);
+    return x;
+}
+
+// Policy::kLoss when the policy has one, false otherwise
+template <class P, class = void>
+struct scan_has_loss : std::false_type {};
+template <class P>
+struct scan_has_loss<P, std::void_t<decltype(P::kLoss)>> : std::bool_constant<P::kLoss> {};
+
 // cap (centre = the record at `mid`, radius = the largest angle from it) of the records [b, e) of one row
 template <class Rec>
 __device__ void hz_cap(const Rec *row, int b, int e, HzCap *out)
@@ -157,11 +175,16 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
     const int64_t s_begin = hz_uniform(a.chunks + 3 * chunk), s_end = hz_uniform(a.chunks + 3 * chunk + 1);
     const unsigned long long n_lanes = (unsigned long long)min<int64_t>(64, a.n_site - site0);
     unsigned long long pairs = 0;
+    constexpr bool kLoss = scan_has_loss<Policy>::value;
+    [[maybe_unused]] double loss_acc = 0.0;             // kLoss: this site's losses of the chunk's storms, summed in storm order
+    [[maybe_unused]] auto terms = [&] { if constexpr (kLoss) return pol.site_terms(my, valid); else return 0; }();
     __syncthreads();
     for (int64_t s = s_begin; s < s_end; ++s) {
         double m = NAN;
+        [[maybe_unused]] bool near = false;             // kLoss: the storm's cap reaches the tile (wave-uniform)
         const int n = hz_uniform(a.rows.cnt + s);
         if (n > 0 && !hz_far(hz_uniform(a.rows.storm + s), tx, ty, tz, ct, st, rt)) {
+            if constexpr (kLoss) near = true;
             const Rec *row = a.rows.rec + s * a.rows.n_seg_max * kHzSeg;
             const HzCap *segs = a.rows.seg + s * a.rows.n_seg_max;
             for (int k = 0; k * kHzSeg < n; ++k) {
@@ -177,6 +200,15 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
             }
         }
         if (a.site_max && valid) a.site_max[site * a.n_trk + s] = m;
+        if constexpr (kLoss) {
+            double t = 0.0;                             // a storm culled for the whole tile: 0, without the butterfly
+            if (near) {
+                const double l = pol.loss(terms, m);
+                loss_acc += l;
+                t = wave_sum(l);
+            }
+            if (lane == 0) pol.tile_loss[tile * a.n_trk + s] = t;
+        }
         if (!isnan(m)) {
             int lo = 0, hi = a.n_bin;                   // k = #thresholds <= m
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (a.thr[mid] <= m) lo = mid + 1; else hi = mid; }
@@ -187,6 +219,7 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
         int32_t c = 0;
         int32_t *out = a.part + (chunk * a.n_site + site) * a.n_bin;
         for (int b = a.n_bin - 1; b >= 0; --b) { c += hist[(b + 1) * 64 + lane]; out[b] = c; }
+        if constexpr (kLoss) pol.site_part[chunk * a.n_site + site] = loss_acc;
     }
     if (lane == 0 && pairs) atomicAdd(a.pairs, pairs * n_lanes);
 }
@@ -205,7 +238,7 @@ __global__ __launch_bounds__(256) void k_hazard_reduce(const int32_t *__restrict
 
 // ---------------------------------------------------------------------------------------------------------------- host
 // ScanWs::d: 0 records, 1 caps (storms, then segments), 2 record counts, 3 partial counts, 4 chunk table + pair counter,
-// 5 the prep kernel's own workspace
+// 5 the prep kernel's own workspace, 6 and 7 the analysis's own (tcr_loss.hip: tile losses, per-chunk site losses)
 template <typename T>
 int scan_grow(tcr_ctx *ctx, ScanWs &w, int i, size_t count)
 {
@@ -234,6 +267,22 @@ int scan_check(tcr_ctx *ctx, const char *who, const Tracks *t, int64_t n_t_max, 
     return 0;
 }
 
+// chunks: every group split into pieces of at most `ch` storms, sized so that the grid has ~8192 waves.  tab: [n_chunk][3] storm
+// begin, storm end, group; gch: [n_group + 1] the first chunk of every group.  A function of the group offsets and n_tile alone.
+template <class Tracks>
+void scan_chunks(const Tracks *t, int64_t n_tile, std::vector<int64_t> &tab, std::vector<int64_t> &gch)
+{
+    const int64_t want = std::max<int64_t>(1, (8192 + n_tile - 1) / n_tile);
+    const int64_t ch = std::max<int64_t>(16, (t->n_trk + want - 1) / want);
+    tab.clear(); gch.assign(1, 0);
+    for (int64_t g = 0; g < t->n_group; ++g) {
+        for (int64_t b = t->group_off[g]; b < t->group_off[g + 1]; b += ch) {
+            tab.push_back(b); tab.push_back(std::min(b + ch, (int64_t)t->group_off[g + 1])); tab.push_back(g);
+        }
+        gch.push_back((int64_t)tab.size() / 3);
+    }
+}
+
 // One call on stream st: chunk table, workspaces, launch, reduction.  launch(args, workspace 5, grid, LDS bytes) enqueues the
 // analysis's prep kernel, then its k_site_scan instantiation, and returns the first launch error.  n_rec: the most records a
 // storm can have; radius_km on a sphere of re_km; extra_bytes: what the prep kernel wants in workspace 5.
@@ -245,16 +294,8 @@ int scan_run(tcr_ctx *ctx, ScanWs &w, const char *who, const Tracks *t, int64_t 
     const int64_t n_trk = t->n_trk, n_group = t->n_group;
     const int64_t n_tile = (n_site + 63) / 64, n_seg_max = (n_rec + kHzSeg - 1) / kHzSeg;
 
-    // chunks: every group split into pieces of at most `ch` storms, sized so that the grid has ~8192 waves
-    const int64_t want = std::max<int64_t>(1, (8192 + n_tile - 1) / n_tile);
-    const int64_t ch = std::max<int64_t>(16, (n_trk + want - 1) / want);
-    std::vector<int64_t> tab, gch(1, 0);
-    for (int64_t g = 0; g < n_group; ++g) {
-        for (int64_t b = t->group_off[g]; b < t->group_off[g + 1]; b += ch) {
-            tab.push_back(b); tab.push_back(std::min(b + ch, (int64_t)t->group_off[g + 1])); tab.push_back(g);
-        }
-        gch.push_back((int64_t)tab.size() / 3);
-    }
+    std::vector<int64_t> tab, gch;
+    scan_chunks(t, n_tile, tab, gch);
     const int64_t n_chunk = (int64_t)tab.size() / 3;
     if (n_tile * n_chunk >= ((int64_t)1 << 31) || n_site * n_group * n_bin >= ((int64_t)1 << 39))
         return fail(ctx, "%s: too many sites x storm chunks for one launch; split the sites", who);

@@ -81,14 +81,20 @@ def _as_planes(arrays, names):
     return planes, conv
 
 
-def _site_scan(entry, planes, conv, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device, make_args):
+def _site_scan(entry, planes, conv, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device, make_args,
+               site_extras=(), more_outputs=()):
     """What the per-site analyses (csrc/tcr_sitescan.h) share in front of the library: checks the sites and groups, puts the
     storms of a group next to each other and the sites in spatial order, runs ``entry + '_dev'`` (torch tensors, on the current
     stream) or ``entry + '_host'`` (NumPy) and returns ``counts``, ``thresholds`` and with return_max ``site_max`` in the
     caller's site and storm order.  planes, conv: of _as_planes.  make_args(tracks, sites, out) -> the entry point's arguments
     after the context: tracks holds the fields every tracks struct has and ``planes``, the pointers of the permuted planes;
     sites = (n_site, lon, lat) and out = (n_bin, thresholds, counts, site_max) are ready to pass on.  The library is not
-    touched before every check here has passed."""
+    touched before every check here has passed.
+
+    An analysis with more per-site inputs or more outputs (loss.py) names them: site_extras, [n_site] arrays (or None) that go
+    through the site permutation with the coordinates; more_outputs, (name, axis) pairs of fp64 outputs along 'trk', 'group' or
+    'site', which come back under their names in the caller's order.  make_args then gets a fourth argument,
+    (pointers of the extras (None stays None), pointers of the outputs)."""
     torch_in = _is_tensor(planes[0])
     if torch_in:
         import torch
@@ -102,6 +108,9 @@ def _site_scan(entry, planes, conv, groups, n_groups, site_lon, site_lat, thr, r
         raise ValueError('site_lon and site_lat must be non-empty and of one length')
     if not bool(xp.isfinite(site_lon).all()) or not bool(xp.isfinite(site_lat).all()):
         raise ValueError('site coordinates must be finite')
+    site_extras = [None if a is None else conv(a).reshape(-1) for a in site_extras]
+    if any(a is not None and a.shape[0] != site_lon.shape[0] for a in site_extras):
+        raise ValueError('a per-site array must hold one value per site')
     n_trk, n_t = int(planes[0].shape[0]), int(planes[0].shape[1])
     g = np.asarray(groups.cpu() if _is_tensor(groups) else groups).reshape(-1)
     if g.shape[0] != n_trk or (n_trk and (g.dtype.kind not in 'iu' or g.min() < 0)):
@@ -124,16 +133,24 @@ def _site_scan(entry, planes, conv, groups, n_groups, site_lon, site_lat, thr, r
         slon, slat = site_lon[site_order].contiguous(), site_lat[site_order].contiguous()
         counts = torch.empty((n_site, n_groups, max(n_bin, 1)), dtype=torch.int32, device=dev)
         smax = torch.empty((n_site, max(n_trk, 1)), dtype=torch.float64, device=dev) if return_max else None
+        extras = [None if a is None else a[site_order].contiguous() for a in site_extras]
+        new = lambda n: torch.empty(max(n, 1), dtype=torch.float64, device=dev)           # noqa: E731
     else:
         planes = [np.ascontiguousarray(a if sorted_ else a[order]) for a in planes]
         slon, slat = np.ascontiguousarray(site_lon[site_order]), np.ascontiguousarray(site_lat[site_order])
         counts = np.empty((n_site, n_groups, max(n_bin, 1)), dtype=np.int32)
         smax = np.empty((n_site, max(n_trk, 1)), dtype=np.float64) if return_max else None
+        extras = [None if a is None else np.ascontiguousarray(a[site_order]) for a in site_extras]
+        new = lambda n: np.empty(max(n, 1), dtype=np.float64)                             # noqa: E731
+    more = [new(dict(trk=n_trk, group=n_groups, site=n_site)[axis]) for _, axis in more_outputs]
     ptr = (lambda a: a.data_ptr()) if torch_in else (lambda a: a.ctypes.data)
     tracks = dict(n_trk=n_trk, n_t=n_t, row_stride=n_t, n_group=n_groups, group_off=group_off.ctypes.data_as(C.POINTER(C.c_int64)),
                   planes=[ptr(a) for a in planes])
-    args = make_args(tracks, (n_site, ptr(slon), ptr(slat)),
-                     (n_bin, thr.ctypes.data_as(_lib.DP), ptr(counts), ptr(smax) if smax is not None else None))
+    args = (tracks, (n_site, ptr(slon), ptr(slat)),
+            (n_bin, thr.ctypes.data_as(_lib.DP), ptr(counts), ptr(smax) if smax is not None else None))
+    if site_extras or more_outputs:
+        args += (([None if a is None else ptr(a) for a in extras], [ptr(a) for a in more]),)
+    args = make_args(*args)
     ctx = _Context(engine, device)
     try:
         if torch_in:
@@ -149,6 +166,16 @@ def _site_scan(entry, planes, conv, groups, n_groups, site_lon, site_lat, thr, r
     out_counts = xp.empty_like(counts)
     out_counts[site_order] = counts
     res = dict(counts=out_counts, thresholds=thr)
+    for (name, axis), a in zip(more_outputs, more):
+        if axis == 'group':
+            res[name] = a[:n_groups]
+            continue
+        out = xp.empty_like(a[:n_trk] if axis == 'trk' else a)
+        if axis == 'site':
+            out[site_order] = a
+        else:
+            out[idx if torch_in else order] = a[:n_trk]
+        res[name] = out
     if return_max and torch_in:
         m = smax[:, :n_trk]
         out = torch.empty_like(m)

@@ -59,6 +59,23 @@ def site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt_s, rmax_km=None, 
     ``thresholds``, and with ``return_max`` ``site_max`` [n_site][n_trk] (m/s; NaN: no sample within r_out_km), in the type and
     on the device of ``lon``.
     """
+    planes, conv, thr, prm = _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
+
+    def make_args(tracks, sites, out):
+        return (C.byref(_tracks_struct(tracks)), C.byref(prm)) + sites + out
+    return hazard._site_scan('tcr_windfield', planes, conv, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device,
+                             make_args)
+
+
+def _tracks_struct(tracks):
+    """tcr_wind_tracks of _site_scan's tracks dict (seven planes, or eight with rmax_km)."""
+    p = tracks.pop('planes') + [None]                      # (no rmax_km plane)
+    return _lib.WindTracks(lon=p[0], lat=p[1], v=p[2], u250=p[3], v250=p[4], u850=p[5], v850=p[6], rmax_km=p[7], **tracks)
+
+
+def _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups):
+    """The footprint's argument checks (ValueError, before the library is touched): (planes, conv, thresholds, tcr_wind_params),
+    shared with loss.portfolio_loss."""
     if len(env) != 4:
         raise ValueError('env must be (u250, v250, u850, v850)')
     planes, conv = hazard._as_planes((lon, lat, v) + tuple(env), 'lon, lat, v and the four env planes')
@@ -102,14 +119,7 @@ def site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt_s, rmax_km=None, 
             planes.append(rm_plane)
     if n_groups is not None and int(n_groups) < 1:
         raise ValueError('n_groups must be >= 1')
-    prm = _lib.WindParams(dt_s=dt_s, ck_cd=ck_cd, r_out_km=r_out_km, rmax_const_km=rm_const, substeps=substeps)
-
-    def make_args(tracks, sites, out):
-        p = tracks.pop('planes') + [None]                  # (no rmax_km plane)
-        trk = _lib.WindTracks(lon=p[0], lat=p[1], v=p[2], u250=p[3], v250=p[4], u850=p[5], v850=p[6], rmax_km=p[7], **tracks)
-        return (C.byref(trk), C.byref(prm)) + sites + out
-    return hazard._site_scan('tcr_windfield', planes, conv, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device,
-                             make_args)
+    return planes, conv, thr, _lib.WindParams(dt_s=dt_s, ck_cd=ck_cd, r_out_km=r_out_km, rmax_const_km=rm_const, substeps=substeps)
 
 
 # ---------------------------------------------------------------------------------------------------------------- CLI
