@@ -410,6 +410,9 @@ def test_gpu_end_to_end_run_downscaling_then_cli(golden_env, built_lib, tmp_path
         assert p.returncode == 0, p.stderr
         assert 'seasonal cycle' in p.stdout
         z = np.load(out)
+        assert set(z.files) == {'track', 'exceed', 'genesis', 'lmi', 'pdi', 'genesis_k', 'lmi_v', 'lmi_k', 'pdi_storm', 'n_storms',
+                                'annual_pdi', 'seasonal_cycle', 'lmi_hist', 'thresholds', 'lmi_bins', 'lon_edges', 'lat_edges', 'cells',
+                                'dt', 'q_scale', 'per_group', 'groups', 'group_file', 'group_year', 'basin', 'files'}
         lon, lat, vmax, groups, gfile, gyear, more = hazard.load_groups([fn], extra=('tc_month', 'tc_basins', 'time'))
         grid = climatology.CellGrid.from_bounds(250, 360, 0, 60, 2)
         mg, mn = (groups, 2) if per_group else (np.zeros_like(groups), 1)

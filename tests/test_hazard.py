@@ -279,6 +279,8 @@ def test_gpu_end_to_end_run_downscaling_then_cli(golden_env, built_lib, tmp_path
     assert p.returncode == 0, p.stderr
     assert 'return period' in p.stdout
     z = np.load(out)
+    assert set(z.files) == {'counts', 'return_period', 'thresholds', 'site_lon', 'site_lat', 'total_years', 'radius_km', 'group_file',
+                            'group_year', 'files'}
     assert int(z['total_years']) == 3 and z['group_year'].tolist() == [2001, 2002, 2003] and z['group_file'].tolist() == [0, 0, 0]
     groups = np.asarray(d['tc_years']).astype(int) - 2001
     m_lo, amb = HN.site_max(lon, lat, vmax, z['site_lon'], z['site_lat'], 100.0)

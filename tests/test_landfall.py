@@ -398,6 +398,11 @@ def test_gpu_end_to_end_run_downscaling_then_cli(golden_env, built_lib, tmp_path
     assert p.returncode == 0, p.stderr
     assert 'return period' in p.stdout
     z = np.load(out)
+    assert set(z.files) == {'n_landfall', 'event_k', 'thresholds', 'groups', 'total_years', 'group_file', 'group_year', 'files',
+                            'counts_first', 'counts_max', 'n_storms', 'return_period_first', 'return_period_max', 'region_names',
+                            'region_box', 'region_counts_first', 'region_counts_max', 'region_n_storms',
+                            'region_return_period_first', 'region_return_period_max', 'event_lon', 'event_lat', 'event_v_landfall',
+                            'event_v_inland', 'site_lon', 'site_lat', 'radius_km', 'site_counts', 'site_return_period'}
     # the in-process API on the same inputs
     lon, lat, vmax, groups, gfile, gyear = hazard.load_groups([fn])
     grid = landfall.read_land(files['land'])

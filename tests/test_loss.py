@@ -174,9 +174,9 @@ def _values(rng, n):
 def _tile_and_chunk(slon, slat, groups, n_groups):
     """The scan's tile of every site (runs of 64 in Morton order) and chunk of every storm (runs of 16 inside a group, which is
     the chunk length below 8192 / n_tile * 16 storms)."""
-    from tropical_cyclone_risk_amd import hazard
+    from tropical_cyclone_risk_amd import sitescan
     tile = np.empty(slon.size, np.int64)
-    tile[hazard._spatial_order(slon, slat, np)] = np.arange(slon.size) // 64
+    tile[sitescan.spatial_order(slon, slat, np)] = np.arange(slon.size) // 64
     chunk = np.empty(groups.size, np.int64)
     base = 0
     for g in range(n_groups):
@@ -436,6 +436,9 @@ def test_gpu_run_downscaling_tracks_then_cli(golden_env, built_lib, tmp_path):
     assert p.returncode == 0, p.stderr
     assert 'average annual loss' in p.stdout and 'AEP' in p.stdout and 'OEP' in p.stdout
     z = np.load(out)
+    assert set(z.files) == {'event_loss', 'year_agg', 'year_max', 'site_loss', 'loss_cost', 'counts', 'thresholds', 'aal',
+                            'return_periods', 'aep', 'oep', 'site_lon', 'site_lat', 'value', 'v_half', 'v_thresh', 'total_years',
+                            'r_out_km', 'substeps', 'rmax_km', 'dt_s', 'group_file', 'group_year', 'files'}
     assert int(z['total_years']) == 3 and z['group_year'].tolist() == [2001, 2002, 2003] and z['group_file'].tolist() == [0, 0, 0]
     assert np.array_equal(z['value'], value) and np.array_equal(z['v_half'], vh)
     api = loss.portfolio_loss(lon, lat, v, env, groups, z['site_lon'], z['site_lat'], value, dt, v_thresh=15.0, v_half=vh,

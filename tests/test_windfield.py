@@ -442,6 +442,8 @@ def test_gpu_run_downscaling_tracks_then_cli(golden_env, built_lib, tmp_path):
     assert p.returncode == 0, p.stderr
     assert 'return period' in p.stdout
     z = np.load(out)
+    assert set(z.files) == {'counts', 'return_period', 'thresholds', 'site_lon', 'site_lat', 'total_years', 'r_out_km', 'substeps',
+                            'rmax_km', 'dt_s', 'group_file', 'group_year', 'files'}
     assert int(z['total_years']) == 3 and z['group_year'].tolist() == [2001, 2002, 2003] and int(z['substeps']) == 4
     assert np.allclose(z['site_lon'], slon, rtol=0, atol=1e-11) and np.allclose(z['site_lat'], slat, rtol=0, atol=1e-11)
     api = windfield.site_wind(lon, lat, v, env, groups, z['site_lon'], z['site_lat'], dt, substeps=4, n_groups=3)

@@ -1,6 +1,5 @@
 """Throughput of the track climatology (csrc/tcr_climatology.hip) on 45 000 tracks (45 years x 1 000) x 361 samples
-(tools/bench_hazard.make_tracks: genesis 8-25 N, 280-340 E, drifting west then recurving north-east, NaN tails after 80-361
-samples), device tensors in and out:
+(bench_common.make_tracks), device tensors in and out:
 
   na_box   the 0.25-degree NA box (lon 260..350, lat 0..60: 360 x 240 cells), thresholds 33 and 50 m/s, one group per year
   globe    the 1-degree globe (360 x 180 cells), the CLI's default thresholds (Saffir-Simpson 1-5), summed over groups
@@ -13,31 +12,16 @@ them.  The GPU's per-storm outputs on that tenth, and its maps of that tenth run
 """
 import ctypes as C
 import json
-import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import bench_common as BC
+from bench_common import timed
 import torch  # noqa: E402
-import bench_hazard as BH  # noqa: E402
 from tests import climatology_numpy as CN  # noqa: E402
 from tropical_cyclone_risk_amd import _lib, climatology  # noqa: E402
-
-
-def timed(fn, st, K=3):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(K):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st); fn(); e1.record(st)
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return float(np.median(ms)), ms
 
 
 def _check(got, want, keys):
@@ -51,24 +35,19 @@ def _check(got, want, keys):
 def main():
     quick = '--quick' in sys.argv
     rng = np.random.default_rng(7)
-    n_years, per_year = (5, 200) if quick else (45, 1000)
-    lon, lat, vmax, years = BH.make_tracks(rng, n_years, per_year)
+    n_years, per_year, _ = BC.sizes(quick)
+    lon, lat, vmax, years = BC.make_tracks(rng, n_years, per_year)
     n_trk, n_t = lon.shape
     live = int((~np.isnan(lon) & ~np.isnan(lat)).sum())
     dev = torch.device('cuda', 0)
     dt = [torch.as_tensor(a, device=dev) for a in (lon, lat, vmax)]
     st = torch.cuda.current_stream(dev)
-    L = _lib.lib()
-    h = C.c_void_p()
-    if L.tcr_ctx_create(0, C.byref(h)) != 0:
-        raise _lib.TcrError(L.tcr_last_error(None).decode())
     sub = np.arange(0, n_trk, 10)
     workloads = (('na_box', climatology.CellGrid.from_bounds(260, 350, 0, 60, 0.25), np.array([33.0, 50.0]), years, n_years),
                  ('globe', climatology.CellGrid.from_bounds(0, 360, -90, 90, 1), np.array(climatology.SAFFIR_SIMPSON),
                   np.zeros(n_trk, np.int64), 1))
-    try:
-        trk = _lib.HazardTracks(n_trk=n_trk, n_t=n_t, row_stride=n_t, lon=dt[0].data_ptr(), lat=dt[1].data_ptr(),
-                                vmax=dt[2].data_ptr(), n_group=0, group_off=None)
+    with BC.open_context() as (L, h):
+        trk = BC.hazard_tracks(dt)
         for name, grid, thr, groups, n_groups in workloads:
             shape = (n_groups, grid.nlat, grid.nlon)
             i32 = dict(dtype=torch.int32, device=dev)
@@ -82,9 +61,8 @@ def main():
             cg = grid._c()
 
             def run():
-                if L.tcr_climatology_dev(h, C.byref(trk), gi.data_ptr(), n_groups, C.byref(cg), thr.size, thr.ctypes.data_as(_lib.DP),
-                                         C.byref(out), C.c_void_p(st.cuda_stream)) != 0:
-                    raise _lib.TcrError(L.tcr_last_error(h).decode())
+                BC.check(L, h, L.tcr_climatology_dev(h, C.byref(trk), gi.data_ptr(), n_groups, C.byref(cg), thr.size,
+                                                     thr.ctypes.data_as(_lib.DP), C.byref(out), C.c_void_p(st.cuda_stream)))
             ms, runs = timed(run, st)
             got = {k: v.cpu().numpy() for k, v in res.items()}
 
@@ -109,8 +87,6 @@ def main():
                   'NumPy restatement %.1f s extrapolated, speed-up %.0fx'
                   % (name, n_trk, n_t, grid.nlon, grid.nlat, n_groups, ms, row['live_samples_per_s'], pairs, np_s, row['speedup']),
                   flush=True)
-    finally:
-        L.tcr_ctx_destroy(h)
 
 
 if __name__ == '__main__':

@@ -1,8 +1,7 @@
 """Throughput of landfall detection (csrc/tcr_landfall.hip) on the reference's 0.125-degree land mask (tests/golden/ref_land.nc):
 
-  detect  45 000 tracks (45 years x 1 000) x 361 samples (tools/bench_hazard.make_tracks: genesis 8-25 N, 280-340 E, drifting west
-          then recurving north-east, NaN tails after 80-361 samples), device tensors in and out, no flags
-  coast   the 10 000-site coast landfall hazard (bench_hazard.coast_sites, R = 100 km) on the device event planes
+  detect  45 000 tracks (45 years x 1 000) x 361 samples (bench_common.make_tracks), device tensors in and out, no flags
+  coast   the 10 000-site coast landfall hazard (bench_common.coast_sites, R = 100 km) on the device event planes
 
 Reports ms per call (device events, median of 3 after a warm-up) and live samples/s, and the NumPy restatement
 (tests/landfall_numpy.py) on one core on a subsample of the tracks, extrapolated to all of them; the GPU events of that subsample
@@ -18,64 +17,41 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import bench_common as BC
+from bench_common import timed
 import torch  # noqa: E402
-import bench_hazard as BH  # noqa: E402
 from tests import landfall_numpy as LN  # noqa: E402
 from tropical_cyclone_risk_amd import _lib, landfall  # noqa: E402
 
 CAP = 16
 
 
-def timed(fn, st, K=3):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(K):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st); fn(); e1.record(st)
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return float(np.median(ms)), ms
-
-
 def main():
     quick = '--quick' in sys.argv
     rng = np.random.default_rng(7)
-    n_years, per_year = (5, 200) if quick else (45, 1000)
-    lon, lat, vmax, groups = BH.make_tracks(rng, n_years, per_year)
+    n_years, per_year, n_coast = BC.sizes(quick)
+    lon, lat, vmax, groups = BC.make_tracks(rng, n_years, per_year)
     n_trk, n_t = lon.shape
     live = int((~np.isnan(lon) & ~np.isnan(lat)).sum())
-    grid = landfall.read_land(os.path.join(ROOT, 'tests', 'golden', 'ref_land.nc'))
+    grid = landfall.read_land(os.path.join(BC.ROOT, 'tests', 'golden', 'ref_land.nc'))
     dev = torch.device('cuda', 0)
     dt = [torch.as_tensor(a, device=dev) for a in (lon, lat, vmax)]
     st = torch.cuda.current_stream(dev)
-    L = _lib.lib()
-    h = C.c_void_p()
-    if L.tcr_ctx_create(0, C.byref(h)) != 0:
-        raise _lib.TcrError(L.tcr_last_error(None).decode())
-    try:
+    with BC.open_context() as (L, h):
         g = _lib.LandGrid(nlon=grid.lon.size, nlat=grid.lat.size, lon=grid.lon.ctypes.data, lat=grid.lat.ctypes.data,
                           land=grid.land.ctypes.data)
-        if L.tcr_land_upload(h, C.byref(g)) != 0:
-            raise _lib.TcrError(L.tcr_last_error(h).decode())
-        trk = _lib.HazardTracks(n_trk=n_trk, n_t=n_t, row_stride=n_t, lon=dt[0].data_ptr(), lat=dt[1].data_ptr(),
-                                vmax=dt[2].data_ptr(), n_group=0, group_off=None)
+        BC.check(L, h, L.tcr_land_upload(h, C.byref(g)))
+        trk = BC.hazard_tracks(dt)
         n_lf = torch.empty(n_trk, dtype=torch.int32, device=dev)
         ev_k = torch.empty((n_trk, CAP), dtype=torch.int32, device=dev)
         planes = [torch.empty((n_trk, CAP), dtype=torch.float64, device=dev) for _ in range(4)]
 
         def detect():
-            if L.tcr_landfall_dev(h, C.byref(trk), CAP, n_lf.data_ptr(), ev_k.data_ptr(), *[p.data_ptr() for p in planes], None,
-                                  C.c_void_p(st.cuda_stream)) != 0:
-                raise _lib.TcrError(L.tcr_last_error(h).decode())
+            BC.check(L, h, L.tcr_landfall_dev(h, C.byref(trk), CAP, n_lf.data_ptr(), ev_k.data_ptr(), *[p.data_ptr() for p in planes],
+                                              None, C.c_void_p(st.cuda_stream)))
         ms, runs = timed(detect, st)
         n = n_lf.cpu().numpy()
         assert n.max() <= CAP, n.max()
-    finally:
-        L.tcr_ctx_destroy(h)
 
     # the restatement on one core, on a subsample; the GPU's events there must equal it bit for bit
     sub = np.arange(0, n_trk, 10)
@@ -97,12 +73,12 @@ def main():
 
     # coast landfall hazard on the device events
     ev = dict(k=ev_k, lon=planes[0], lat=planes[1], v_landfall=planes[2], v_inland=planes[3], n_landfall=n_lf)
-    slon, slat = BH.coast_sites(rng, 1000 if quick else 10000)
+    slon, slat = BC.coast_sites(rng, n_coast)
     ts = [torch.as_tensor(a, device=dev) for a in (slon, slat)]
     out = {}
 
     def site():
-        out['r'] = landfall.landfall_site_hazard(ev, groups, ts[0], ts[1], radius_km=BH.R_KM, thresholds=BH.THR)
+        out['r'] = landfall.landfall_site_hazard(ev, groups, ts[0], ts[1], radius_km=BC.R_KM, thresholds=BC.THR)
     t0 = time.perf_counter()
     sms, sruns = timed(site, st)
     counts = out['r']['counts'].cpu().numpy()

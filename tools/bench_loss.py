@@ -1,5 +1,5 @@
 """Cost of the portfolio loss (csrc/tcr_loss.hip) next to the wind footprint it is fused into, on tools/bench_windfield.py's
-site sets and tracks (45 000 tracks x 361 samples, r_out = 500 km, substeps 1, c = 1, rm modelled):
+site sets and tracks (bench_common; 45 000 tracks x 361 samples, r_out = 500 km, substeps 1, c = 1, rm modelled):
 
   coast  10^4 coast-like sites          grid   the 0.25-degree NA grid (87 001 sites)
 
@@ -24,28 +24,25 @@ import types
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import bench_common as BC
+from bench_common import ROOT
+import torch  # noqa: E402  (importing it does not touch the GPU)
+from tropical_cyclone_risk_amd import _lib, loss, sitescan, windfield  # noqa: E402
 
 SEED = 7
+THR = BC.THR
 
 
 def workload(quick):
-    from bench_hazard import coast_sites, grid_sites
-    from bench_windfield import make_storms
     rng = np.random.default_rng(SEED)
-    n_years, per_year = (5, 200) if quick else (45, 1000)
-    lon, lat, v, env, groups = make_storms(rng, n_years, per_year)
-    sites = (('coast', coast_sites(rng, 1000 if quick else 10000)), ('grid', grid_sites()))
+    n_years, per_year, n_coast = BC.sizes(quick)
+    lon, lat, v, env, groups = BC.make_storms(rng, n_years, per_year)
+    sites = (('coast', BC.coast_sites(rng, n_coast)), ('grid', BC.grid_sites()))
     return lon, lat, v, env, groups, sites
 
 
 def windfield_only(lib_path, quick):
     """Child process: tcr_windfield_dev of the library at lib_path on both site sets; one JSON line."""
-    import torch
-    from tropical_cyclone_risk_amd import _lib
-    import bench_windfield as BW
     _lib._pin_hip_runtime()
     L = C.CDLL(lib_path)
     L.tcr_last_error.restype = C.c_char_p
@@ -58,16 +55,13 @@ def windfield_only(lib_path, quick):
     lon, lat, v, env, groups, sites = workload(quick)
     dev = torch.device('cuda', 0)
     dt = [torch.as_tensor(a, device=dev) for a in [lon, lat, v] + env]
-    h = C.c_void_p()
-    if L.tcr_ctx_create(0, C.byref(h)) != 0:
-        raise RuntimeError(L.tcr_last_error(None).decode())
+    trk = BC.wind_tracks(dt, groups)
+    prm = _lib.WindParams(dt_s=3600.0, ck_cd=1.0, r_out_km=500.0, rmax_const_km=0.0, substeps=1)
     out = {}
-    try:
+    with BC.open_context(L) as (L, h):
         for name, (slon, slat) in sites:
-            ms, runs, pairs, counts = BW.run_gpu(L, h, dt, groups, slon, slat, 1)
+            ms, runs, pairs, counts = BC.time_site_scan(L, h, 'tcr_windfield', trk, (C.byref(prm),), (), slon, slat)
             out[name] = dict(ms=round(ms, 3), runs=[round(x, 3) for x in runs], pairs=pairs, counts_sum=int(counts.sum()))
-    finally:
-        L.tcr_ctx_destroy(h)
     print('RESULT ' + json.dumps(out), flush=True)
 
 
@@ -77,19 +71,6 @@ def child(lib_path, quick):
     if p.returncode != 0:
         raise SystemExit('windfield run of %s failed (%d):\n%s' % (lib_path, p.returncode, p.stderr[-2000:]))
     return json.loads([l for l in p.stdout.splitlines() if l.startswith('RESULT ')][-1][7:])
-
-
-def timed(st, fn, K=3):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(K):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st); res = fn(); e1.record(st)
-        torch.cuda.synchronize()
-        ms.append(round(e0.elapsed_time(e1), 3))
-    return ms, res
 
 
 def main():
@@ -108,7 +89,6 @@ def main():
         lines.append(text)
 
     # (a) one process per library, one after the other, before this process touches the GPU
-    from tropical_cyclone_risk_amd import _lib
     a_parent, a_this = child(parent_lib, quick), child(_lib.LIB_PATH, quick)
     for name in ('coast', 'grid'):
         p, t = a_parent[name], a_this[name]
@@ -119,46 +99,39 @@ def main():
                              parent_median=p['ms'], this_median=t['ms'], parent_slowest=max(p['runs']), parent_spread=round(spread, 3),
                              same_pairs_and_counts=same, condition_1_met=bool(ok and same))))
 
-    import torch
-    from tropical_cyclone_risk_amd import hazard, loss, windfield
     lon, lat, v, env, groups, sites = workload(quick)
     n_groups = int(groups.max()) + 1
     dev = torch.device('cuda', 0)
     dt = [torch.as_tensor(a, device=dev) for a in [lon, lat, v] + env]
     st = torch.cuda.current_stream(dev)
-    L = _lib.lib()
-    h = C.c_void_p()
-    if L.tcr_ctx_create(0, C.byref(h)) != 0:
-        raise _lib.TcrError(L.tcr_last_error(None).decode())
-    eng = types.SimpleNamespace(h=h)
-    THR = hazard.DEFAULT_THRESHOLDS
-    try:
+    trk = BC.wind_tracks(dt, groups)
+    n_trk = lon.shape[0]
+    keep = {}                           # the last result of a timed function
+
+    def ms_runs(fn):
+        return [round(x, 3) for x in BC.timed(fn, st)[1]]
+    with BC.open_context() as (L, h):
+        eng = types.SimpleNamespace(h=h)
         for name, (slon, slat) in sites:
             n_site = len(slon)
             value = np.random.default_rng(SEED + 1).lognormal(13.0, 1.5, n_site)
             tl, ta, tv = (torch.as_tensor(x, device=dev) for x in (slon, slat, value))
             # (b) the entry point itself, sites in spatial order
-            order = hazard._spatial_order(tl, ta, torch)
+            order = sitescan.spatial_order(tl, ta, torch)
             sl, sa, sv = tl[order].contiguous(), ta[order].contiguous(), tv[order].contiguous()
-            group_off = np.zeros(n_groups + 1, np.int64)
-            group_off[1:] = np.cumsum(np.bincount(groups, minlength=n_groups))
-            n_trk, n_t = lon.shape
-            trk = _lib.WindTracks(n_trk=n_trk, n_t=n_t, row_stride=n_t, lon=dt[0].data_ptr(), lat=dt[1].data_ptr(), v=dt[2].data_ptr(),
-                                  u250=dt[3].data_ptr(), v250=dt[4].data_ptr(), u850=dt[5].data_ptr(), v850=dt[6].data_ptr(),
-                                  rmax_km=None, n_group=n_groups, group_off=group_off.ctypes.data_as(C.POINTER(C.c_int64)))
             wprm = _lib.WindParams(dt_s=3600.0, ck_cd=1.0, r_out_km=500.0, rmax_const_km=0.0, substeps=1)
             lprm = _lib.LossParams(v_thresh=loss.V_THRESH, v_half=loss.V_HALF)
             counts = torch.empty((n_site, n_groups, THR.size), dtype=torch.int32, device=dev)
             ev, agg, mx, sl_ = (torch.empty(n, dtype=torch.float64, device=dev) for n in (n_trk, n_groups, n_groups, n_site))
 
             def direct():
-                if L.tcr_loss_dev(h, C.byref(trk), C.byref(wprm), C.byref(lprm), n_site, sl.data_ptr(), sa.data_ptr(), sv.data_ptr(),
-                                  None, THR.size, THR.ctypes.data_as(_lib.DP), counts.data_ptr(), ev.data_ptr(), agg.data_ptr(),
-                                  mx.data_ptr(), sl_.data_ptr(), C.c_void_p(st.cuda_stream)) != 0:
-                    raise _lib.TcrError(L.tcr_last_error(h).decode())
-            b_ms, _ = timed(st, direct)
+                BC.check(L, h, L.tcr_loss_dev(h, C.byref(trk), C.byref(wprm), C.byref(lprm), n_site, sl.data_ptr(), sa.data_ptr(),
+                                              sv.data_ptr(), None, THR.size, THR.ctypes.data_as(_lib.DP), counts.data_ptr(), ev.data_ptr(),
+                                              agg.data_ptr(), mx.data_ptr(), sl_.data_ptr(), C.c_void_p(st.cuda_stream)))
+            b_ms = ms_runs(direct)
             kw = dict(r_out_km=500.0, substeps=1, ck_cd=1.0, thresholds=THR, engine=eng, n_groups=n_groups)
-            api_ms, res = timed(st, lambda: loss.portfolio_loss(dt[0], dt[1], dt[2], dt[3:7], groups, tl, ta, tv, 3600.0, **kw))
+            api_ms = ms_runs(lambda: keep.update(res=loss.portfolio_loss(dt[0], dt[1], dt[2], dt[3:7], groups, tl, ta, tv, 3600.0, **kw)))
+            res = keep['res']
             assert torch.equal(res['event_loss'], ev) and torch.equal(res['year_agg'], agg) and torch.equal(res['year_max'], mx)
             row = dict(what='(b) tcr_loss_dev', workload=name, sites=n_site, tracks=n_trk, loss_ms_runs=b_ms,
                        loss_median=float(np.median(b_ms)), portfolio_loss_api_ms_runs=api_ms, api_median=float(np.median(api_ms)),
@@ -176,10 +149,11 @@ def main():
                 x3 = x * x * x
                 T = x3.div_(1.0 + x3).mul_(tv[:, None])
                 e = T.sum(dim=0)
-                return dict(event_loss=e, site_loss=T.sum(dim=1), counts=w['counts'],
-                            year_agg=torch.zeros(n_groups, dtype=torch.float64, device=dev).index_add_(0, g, e),
-                            year_max=torch.zeros(n_groups, dtype=torch.float64, device=dev).index_reduce_(0, g, e, 'amax'))
-            c_ms, un = timed(st, unfused)
+                keep['un'] = dict(event_loss=e, site_loss=T.sum(dim=1), counts=w['counts'],
+                                  year_agg=torch.zeros(n_groups, dtype=torch.float64, device=dev).index_add_(0, g, e),
+                                  year_max=torch.zeros(n_groups, dtype=torch.float64, device=dev).index_reduce_(0, g, e, 'amax'))
+            c_ms = ms_runs(unfused)
+            un = keep.pop('un')
             err = float(((un['event_loss'] - res['event_loss']).abs() / res['event_loss'].clamp(min=1e-300)).max())
             assert err <= (n_site + 16) * 2.0 ** -52 and torch.equal(un['counts'], res['counts']), err
             emit(json.dumps(dict(what='(c) site_wind(return_max) + torch', workload=name, unfused_ms_runs=c_ms,
@@ -188,8 +162,6 @@ def main():
                                  condition_2_met=bool(np.median(b_ms) <= np.median(c_ms)))))
             del un
             torch.cuda.empty_cache()
-    finally:
-        L.tcr_ctx_destroy(h)
     if not quick:
         with open(out_fn, 'w') as f:
             f.write('\n'.join(lines) + '\n')

@@ -1,11 +1,9 @@
 """Throughput of the wind-footprint kernels (csrc/tcr_windfield.hip) on two site sets, against the NumPy restatement on a subsample:
 
-  coast  10^4 coast-like sites (tools/bench_hazard.py's jittered Gulf / US East coast polyline) x 45 000 tracks (45 years x 1 000)
-         x 361 samples
-  grid   the 0.25-degree NA grid (lon 260..350, lat 0..60: 361 x 241 = 87 001 sites) x the same tracks
+  coast  10^4 coast-like sites (bench_common.coast_sites) x 45 000 tracks (45 years x 1 000) x 361 samples
+  grid   the 0.25-degree NA grid (bench_common.grid_sites: 87 001 sites) x the same tracks
 
-Tracks are bench_hazard's seeded random walks (NaN tails after 80-361 samples) with v a bounded random walk in 15-75 m/s and
-env winds of N(0, 8 m/s).  r_out = 500 km, substeps 1 and 4, c = 1, rm modelled.  Reports ms per call (device events, median of 3
+Tracks are bench_common.make_storms' seeded random walks.  r_out = 500 km, substeps 1 and 4, c = 1, rm modelled.  Reports ms per call (device events, median of 3
 after a warm-up), the raw pairs (sites x samples and sub-samples), the evaluated pairs left after culling (tcr_windfield_pairs)
 and the culled fraction, evaluated pairs/s, and the restatement (tests/windfield_numpy.py) on a few sites on one core,
 extrapolated to all sites; the GPU result on those sites is checked against it.
@@ -14,70 +12,25 @@ extrapolated to all sites; the GPU result on those sites is checked against it.
 """
 import ctypes as C
 import json
-import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import bench_common as BC
+from bench_common import THR
 import torch  # noqa: E402
-from bench_hazard import coast_sites, grid_sites, make_tracks  # noqa: E402
 from tests import windfield_numpy as WN  # noqa: E402
-from tropical_cyclone_risk_amd import _lib, hazard, windfield  # noqa: E402
+from tropical_cyclone_risk_amd import _lib, windfield  # noqa: E402
 
 R_OUT = 500.0
 DT = 3600.0
-THR = np.arange(10, 81, 5).astype(np.float64)
 
 
-def make_storms(rng, n_years, per_year):
-    lon, lat, _, groups = make_tracks(rng, n_years, per_year)
-    n, n_t = lon.shape
-    v = np.clip(35 + np.cumsum(rng.normal(0.0, 1.0, (n, n_t)), axis=1), 15, 75)
-    env = [rng.normal(0, 8, (n, n_t)) for _ in range(4)]
-    tail = np.isnan(lon)
-    v[tail] = np.nan
-    for e in env:
-        e[tail] = np.nan
-    return lon, lat, v, env, groups
-
-
-def run_gpu(L, h, dt, groups, slon, slat, substeps, K=3):
-    dev = dt[0].device
-    n_trk, n_t = dt[0].shape
-    n_groups = int(groups.max()) + 1
-    group_off = np.zeros(n_groups + 1, np.int64)
-    group_off[1:] = np.cumsum(np.bincount(groups, minlength=n_groups))
-    order = hazard._spatial_order(torch.as_tensor(slon, device=dev), torch.as_tensor(slat, device=dev), torch)
-    sl, sa = torch.as_tensor(slon, device=dev)[order].contiguous(), torch.as_tensor(slat, device=dev)[order].contiguous()
-    counts = torch.empty((len(slon), n_groups, THR.size), dtype=torch.int32, device=dev)
-    trk = _lib.WindTracks(n_trk=n_trk, n_t=n_t, row_stride=n_t, lon=dt[0].data_ptr(), lat=dt[1].data_ptr(), v=dt[2].data_ptr(),
-                          u250=dt[3].data_ptr(), v250=dt[4].data_ptr(), u850=dt[5].data_ptr(), v850=dt[6].data_ptr(), rmax_km=None,
-                          n_group=n_groups, group_off=group_off.ctypes.data_as(C.POINTER(C.c_int64)))
+def run_gpu(L, h, trk, slon, slat, substeps):
+    """bench_common.time_site_scan of tcr_windfield (r_out = 500 km, c = 1, rm modelled)."""
     prm = _lib.WindParams(dt_s=DT, ck_cd=1.0, r_out_km=R_OUT, rmax_const_km=0.0, substeps=substeps)
-    st = torch.cuda.current_stream(dev)
-
-    def launch():
-        if L.tcr_windfield_dev(h, C.byref(trk), C.byref(prm), len(slon), sl.data_ptr(), sa.data_ptr(), THR.size,
-                               THR.ctypes.data_as(_lib.DP), counts.data_ptr(), None, C.c_void_p(st.cuda_stream)) != 0:
-            raise _lib.TcrError(L.tcr_last_error(h).decode())
-    launch()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(K):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st); launch(); e1.record(st)
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    pairs = C.c_int64()
-    if L.tcr_windfield_pairs(h, C.byref(pairs)) != 0:
-        raise _lib.TcrError(L.tcr_last_error(h).decode())
-    out = torch.empty_like(counts)
-    out[order] = counts
-    return float(np.median(ms)), ms, int(pairs.value), out.cpu().numpy()
+    return BC.time_site_scan(L, h, 'tcr_windfield', trk, (C.byref(prm),), (), slon, slat)
 
 
 def numpy_check(recs, dt, groups, slon, slat, substeps, idx):
@@ -102,25 +55,22 @@ def numpy_check(recs, dt, groups, slon, slat, substeps, idx):
 def main():
     quick = '--quick' in sys.argv
     rng = np.random.default_rng(7)
-    n_years, per_year = (5, 200) if quick else (45, 1000)
-    lon, lat, v, env, groups = make_storms(rng, n_years, per_year)
+    n_years, per_year, n_coast = BC.sizes(quick)
+    lon, lat, v, env, groups = BC.make_storms(rng, n_years, per_year)
     n = WN.track_length(lon, lat, v, env)
     dev = torch.device('cuda', 0)
     dt = [torch.as_tensor(a, device=dev) for a in [lon, lat, v] + env]
-    L = _lib.lib()
-    h = C.c_void_p()
-    if L.tcr_ctx_create(0, C.byref(h)) != 0:
-        raise _lib.TcrError(L.tcr_last_error(None).decode())
-    sites = (('coast', coast_sites(rng, 1000 if quick else 10000)), ('grid', grid_sites()))
+    trk = BC.wind_tracks(dt, groups)
+    sites = (('coast', BC.coast_sites(rng, n_coast)), ('grid', BC.grid_sites()))
     results = []
-    try:
+    with BC.open_context() as (L, h):
         for substeps in (1, 4):
             records = int(np.where(n >= 2, (n - 1) * substeps + 1, 0).sum())
             # the restatement on a tenth of the storms, scaled to all of them
             sub = np.arange(0, lon.shape[0], 10)
             recs = WN.samples(lon[sub], lat[sub], v[sub], [e[sub] for e in env], DT, substeps=substeps)
             for name, (slon, slat) in sites:
-                ms, all_ms, pairs, counts = run_gpu(L, h, dt, groups, slon, slat, substeps)
+                ms, all_ms, pairs, counts = run_gpu(L, h, trk, slon, slat, substeps)
                 raw = len(slon) * records
                 idx = np.sort(np.random.default_rng(1).choice(len(slon), 3, replace=False))
                 hit = np.nonzero(counts.sum(axis=(1, 2)))[0]
@@ -137,8 +87,6 @@ def main():
                            check='gpu == restatement (tolerance) on the checked sites x storms')
                 results.append(row)
                 print(json.dumps(row), flush=True)
-    finally:
-        L.tcr_ctx_destroy(h)
     for r in results:
         print('%-5s substeps %d, %6d sites: %9.2f ms, evaluated %.3g pairs/s (%.2f %% of %.3g pairs culled); restatement '
               '%.0f s extrapolated, speed-up %.0fx' % (r['workload'], r['substeps'], r['sites'], r['gpu_ms'], r['evaluated_pairs_per_s'],

@@ -1,0 +1,273 @@
+"""What the analyses of track files (hazard, landfall, climatology, windfield, loss) share: NumPy-or-torch planes, the library
+context of one call, the group index of the storms, reading (file, year) groups from track files, and the pieces of their
+command lines.  The per-site scan they share on top of this is sitescan.py."""
+import argparse
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+DEFAULT_THRESHOLDS = np.arange(10, 81, 5).astype(np.float64)
+ENV_VARS = ('u250_trks', 'v250_trks', 'u850_trks', 'v850_trks')
+
+
+# ------------------------------------------------------------------------------------------------------------- arrays
+def is_tensor(x):
+    return type(x).__module__.startswith('torch')
+
+
+def to_numpy(a):
+    return np.asarray(a.cpu() if is_tensor(a) else a)
+
+
+class Flavour:
+    """NumPy arrays, or torch tensors on one device, after a first array: the array module ``xp``, the device ``dev`` (None for
+    NumPy), and what an analysis does in either flavour: convert, allocate, make contiguous, take a pointer."""
+    _KINDS = {'u1': 'uint8', 'i4': 'int32', 'i8': 'int64', 'f8': 'float64'}
+
+    def __init__(self, first):
+        self.torch = is_tensor(first)
+        if self.torch:
+            import torch
+            self.xp, self.dev = torch, first.device
+        else:
+            self.xp, self.dev = np, None
+
+    def conv(self, a):
+        """a as fp64 of this flavour."""
+        if self.torch:
+            return self.xp.as_tensor(a, dtype=self.xp.float64, device=self.dev)
+        return np.asarray(to_numpy(a), dtype=np.float64)
+
+    def new(self, shape, kind):
+        """An uninitialised array; kind: 'u1', 'i4', 'i8' or 'f8'."""
+        if self.torch:
+            return self.xp.empty(shape, dtype=getattr(self.xp, self._KINDS[kind]), device=self.dev)
+        return np.empty(shape, dtype=kind)
+
+    def contiguous(self, a):
+        return a.contiguous() if self.torch else np.ascontiguousarray(a)
+
+    def ptr(self, a):
+        return a.data_ptr() if self.torch else a.ctypes.data
+
+    def context(self, engine, device):
+        """The Context of a call on arrays of this flavour (device: the device index of a NumPy call)."""
+        return Context(engine, self.dev if self.torch else device)
+
+
+def as_planes(arrays, names):
+    """The track planes as fp64 arrays of the type and on the device of the first: (planes, their Flavour)."""
+    fl = Flavour(arrays[0])
+    planes = [fl.conv(a) for a in arrays]
+    if planes[0].ndim != 2 or any(tuple(p.shape) != tuple(planes[0].shape) for p in planes):
+        raise ValueError('%s must be [n_trk][n_t] arrays of one shape' % names)
+    return planes, fl
+
+
+# ------------------------------------------------------------------------------------------------------------ context
+class Context:
+    """The caller's engine (anything with a library handle `.h`), or a context of our own for one ``with`` block.  device: the
+    device index (the NumPy flavour: `call` runs the ``_host`` entry points), or the torch device of the inputs (`call` runs the
+    ``_dev`` entry points on its current stream)."""
+
+    def __init__(self, engine, device):
+        self.L = _lib.lib()
+        self.dev = None if isinstance(device, (int, np.integer)) else device
+        if self.dev is not None:
+            import torch
+            self._stream = lambda: torch.cuda.current_stream(self.dev)
+            device = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
+        self.own = engine is None
+        if self.own:
+            h = C.c_void_p()
+            if self.L.tcr_ctx_create(int(device), C.byref(h)) != 0:
+                raise _lib.TcrError(self.L.tcr_last_error(None).decode())
+            self.h = h
+        else:
+            self.h = engine.h
+
+    def check(self, rc):
+        if rc != 0:
+            raise _lib.TcrError(self.L.tcr_last_error(self.h).decode())
+
+    def call(self, entry, *args):
+        if self.dev is not None:
+            self.check(getattr(self.L, entry + '_dev')(self.h, *args, C.c_void_p(self._stream().cuda_stream)))
+        else:
+            self.check(getattr(self.L, entry + '_host')(self.h, *args))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self.own and self.h:
+            if self.dev is not None:
+                self._stream().synchronize()                    # the context's workspaces go with it
+            self.L.tcr_ctx_destroy(self.h)
+            self.h = None
+
+
+# ------------------------------------------------------------------------------------------------------------- groups
+def group_index(groups, n_trk, n_groups=None, bad='groups must hold one non-negative integer per storm',
+                over='a group index is >= n_groups'):
+    """(int64 group of every storm, n_groups): one non-negative integer per storm, n_groups by default max + 1 (1 without
+    storms), every index < n_groups.  bad, over: the caller's ValueError texts."""
+    g = to_numpy(groups).reshape(-1)
+    if g.shape[0] != n_trk or (n_trk and (g.dtype.kind not in 'iu' or g.min() < 0)):
+        raise ValueError(bad)
+    g = g.astype(np.int64)
+    n_groups = int(n_groups if n_groups is not None else (g.max() + 1 if n_trk else 1))
+    if n_trk and g.max() >= n_groups:
+        raise ValueError(over)
+    return g, n_groups
+
+
+# -------------------------------------------------------------------------------------------------------- track files
+def load_groups(files, extra=()):
+    """Read the track files and number their (file, year) groups: every year of every file's `year` coordinate is one group,
+    years without storms included.  Returns lon, lat, vmax [n_trk][n_t], the group of every storm, group_file and group_year
+    [n_group] (the group -> (file index, year) map).  extra: names of further variables of the files; when given, a seventh
+    element {name: [one array per file]} follows."""
+    from . import io as tio
+    lon, lat, vmax, groups, gfile, gyear = [], [], [], [], [], []
+    more = {name: [] for name in extra}
+    for k, fn in enumerate(files):
+        d = tio.read_tracks(fn)
+        for name in extra:
+            more[name].append(np.asarray(d[name]))
+        years = np.asarray(d['year']).astype(np.int64).reshape(-1)
+        tc_years = np.asarray(d['tc_years']).astype(np.int64).reshape(-1)
+        pos = {int(y): i for i, y in enumerate(years)}
+        if not set(int(y) for y in tc_years) <= set(pos):
+            raise ValueError('%s: a storm year is not in the file\'s year coordinate' % fn)
+        groups.append(len(gfile) + np.array([pos[int(y)] for y in tc_years], dtype=np.int64))
+        gfile += [k] * len(years)
+        gyear += list(years)
+        for dst, key in ((lon, 'lon_trks'), (lat, 'lat_trks'), (vmax, 'vmax_trks')):
+            dst.append(np.asarray(d[key], dtype=np.float64))
+    n_t = {a.shape[1] for a in lon}
+    if len(n_t) != 1:
+        raise ValueError('the track files have different time axes: %s' % sorted(n_t))
+    res = (np.concatenate(lon), np.concatenate(lat), np.concatenate(vmax), np.concatenate(groups),
+           np.array(gfile, dtype=np.int64), np.array(gyear, dtype=np.int64))
+    return res + (more,) if extra else res
+
+
+def sample_spacing(times):
+    """dt (s) of the track files' `time` axes (one array per file): time[1] - time[0], uniform to a relative 1e-9 and equal in
+    every file; a file of one sample takes the namelist's output interval."""
+    from . import namelist
+    dts = []
+    for t in times:
+        t = np.asarray(t, dtype=np.float64).reshape(-1)
+        if t.size < 2:
+            dts.append(float(namelist.output_interval_s))
+            continue
+        dt = float(t[1] - t[0])
+        if not dt > 0 or np.any(np.abs(np.diff(t) - dt) > 1e-9 * dt):
+            raise ValueError('the time axis of a track file is not uniform')
+        dts.append(dt)
+    if any(abs(d - dts[0]) > 1e-9 * dts[0] for d in dts):
+        raise ValueError('the track files have different sample spacings: %s' % sorted(set(dts)))
+    return dts[0]
+
+
+def load_wind_planes(files):
+    """What the wind footprint reads from track files: lon, lat, vmax, v [n_trk][n_t], env (the four ENV_VARS planes), the
+    groups, group_file and group_year of load_groups, and the sample spacing dt (s)."""
+    lon, lat, vmax, groups, gfile, gyear, more = load_groups(files, extra=('v_trks',) + ENV_VARS + ('time',))
+    v, *env = (np.concatenate([np.asarray(a, dtype=np.float64) for a in more[k]]) for k in ('v_trks',) + ENV_VARS)
+    return lon, lat, vmax, v, env, groups, gfile, gyear, sample_spacing(more['time'])
+
+
+def group_meta(files, gfile, gyear):
+    """The group -> (file, year) map as every analysis saves it: the tail of its np.savez."""
+    return dict(group_file=gfile, group_year=gyear, files=np.array([str(f) for f in files]))
+
+
+# ---------------------------------------------------------------------------------------------------------------- CLI
+def parse_range(text, what):
+    """LO:HI:STEP, both ends included."""
+    try:
+        lo, hi, step = (float(x) for x in text.split(':'))
+    except ValueError:
+        raise argparse.ArgumentTypeError('%s: expected LO:HI:STEP, got %r' % (what, text))
+    if not step > 0 or hi < lo:
+        raise argparse.ArgumentTypeError('%s: need STEP > 0 and HI >= LO, got %r' % (what, text))
+    return lo + step * np.arange(int(np.floor((hi - lo) / step + 1e-9)) + 1)
+
+
+def parse_site(text):
+    try:
+        lon, lat = (float(x) for x in text.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError('--site: expected LON,LAT, got %r' % text)
+    return lon, lat
+
+
+def parse_grid(text):
+    parts = text.split(',')
+    if len(parts) != 2:
+        raise argparse.ArgumentTypeError('--grid: expected LON0:LON1:DLON,LAT0:LAT1:DLAT, got %r' % text)
+    return parse_range(parts[0], '--grid lon'), parse_range(parts[1], '--grid lat')
+
+
+def add_track_args(p, out_default):
+    p.add_argument('tracks', nargs='+', help='track files (ensemble members); every year of every file is one group')
+    p.add_argument('--out', default=out_default)
+    p.add_argument('--device', type=int, default=0)
+
+
+def add_site_args(p):
+    p.add_argument('--site', type=parse_site, action='append', default=[], metavar='LON,LAT',
+                   help='repeatable; write --site=LON,LAT when LON is negative')
+    p.add_argument('--sites', metavar='FILE.csv', help='one LON,LAT per line (lines that are not two numbers are skipped)')
+    p.add_argument('--grid', type=parse_grid, metavar='LON0:LON1:DLON,LAT0:LAT1:DLAT')
+
+
+def add_footprint_args(p):
+    p.add_argument('--rmax-km', type=float, default=None, help='constant radius of maximum wind (default: Willoughby et al. 2006)')
+    p.add_argument('--r-out-km', type=float, default=500.0)
+    p.add_argument('--substeps', type=int, default=1, help='evaluation points per sample interval (1 = the samples only)')
+    p.add_argument('--ck-cd', type=float, default=None, help='Ck / Cd of the profile (default: the namelist\'s)')
+
+
+def add_threshold_arg(p):
+    p.add_argument('--thresholds', type=lambda t: parse_range(t, '--thresholds'), default=DEFAULT_THRESHOLDS, metavar='LO:HI:STEP')
+
+
+def read_sites_csv(fn):
+    out = []
+    for line in open(fn):
+        f = line.replace(';', ',').split(',')
+        try:
+            if len(f) >= 2:
+                out.append((float(f[0]), float(f[1])))
+        except ValueError:
+            pass
+    return out
+
+
+def collect_sites(args):
+    """The sites of --site, --sites and --grid, in that order: (lon [n], lat [n])."""
+    pts = list(args.site)
+    if args.sites:
+        pts += read_sites_csv(args.sites)
+    lon = [p[0] for p in pts]
+    lat = [p[1] for p in pts]
+    if args.grid is not None:
+        glon, glat = np.meshgrid(args.grid[0], args.grid[1])
+        lon += list(glon.ravel())
+        lat += list(glat.ravel())
+    return np.array(lon, dtype=np.float64), np.array(lat, dtype=np.float64)
+
+
+def print_return_periods(thresholds, site_lon, site_lat, rp):
+    """The return-period table of up to 10 sites (more: nothing)."""
+    if site_lon.size > 10:
+        return
+    print('return period (years) by threshold (m/s): ' + ' '.join('%6g' % t for t in thresholds))
+    for i in range(site_lon.size):
+        print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%6.3g' % v for v in rp[i]))

@@ -22,8 +22,8 @@ import sys
 
 import numpy as np
 
-from . import _lib, hazard
-from .hazard import _Context, _is_tensor
+from . import _lib, analysis
+from .analysis import sample_spacing, to_numpy as _np
 
 Q_SCALE = 1024.0                        # pdi / Q_SCALE * dt = PDI in m^3 s^-2
 V_MAX = 400.0                           # vmax outside [0, V_MAX] (m/s) is rejected
@@ -81,18 +81,11 @@ class CellGrid:
                                                                                     self.dlat, self.nlat)
 
 
-def _np(a):
-    return np.asarray(a.cpu() if _is_tensor(a) else a)
-
-
 def _group_index(groups, n_trk, n_groups):
-    g = _np(groups).reshape(-1)
-    if g.shape[0] != n_trk or (n_trk and (g.dtype.kind not in 'iu' or g.min() < 0)):
-        raise ValueError('groups must hold one non-negative integer per storm')
-    g = g.astype(np.int64)
-    n_groups = int(n_groups if n_groups is not None else (g.max() + 1 if n_trk else 1))
-    if n_groups < 1 or n_groups >= 1 << 31 or (n_trk and g.max() >= n_groups):
-        raise ValueError('a group index is >= n_groups (or n_groups is not in [1, 2^31))')
+    over = 'a group index is >= n_groups (or n_groups is not in [1, 2^31))'
+    g, n_groups = analysis.group_index(groups, n_trk, n_groups, over=over)
+    if not 1 <= n_groups < 1 << 31:
+        raise ValueError(over)
     return g, n_groups
 
 
@@ -116,18 +109,9 @@ def track_climatology(lon, lat, vmax, groups, grid, thresholds=(), n_groups=None
     """
     if not isinstance(grid, CellGrid):
         grid = CellGrid(*grid)
-    torch_in = _is_tensor(lon)
-    if torch_in:
-        import torch
-        xp = torch
-        dev = lon.device
-        lon, lat, vmax = (torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous() for a in (lon, lat, vmax))
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-    else:
-        xp = np
-        lon, lat, vmax = (np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in (lon, lat, vmax))
-    if lon.ndim != 2 or tuple(lat.shape) != tuple(lon.shape) or tuple(vmax.shape) != tuple(lon.shape):
-        raise ValueError('lon, lat and vmax must be [n_trk][n_t] arrays of one shape')
+    (lon, lat, vmax), fl = analysis.as_planes((lon, lat, vmax), 'lon, lat and vmax')
+    lon, lat, vmax = (fl.contiguous(a) for a in (lon, lat, vmax))
+    xp, new, ptr = fl.xp, fl.new, fl.ptr
     n_trk, n_t = int(lon.shape[0]), int(lon.shape[1])
     if n_t < 1 or n_trk * n_t > MAX_SAMPLES:
         raise ValueError('the tracks need 1 <= n_t and n_trk * n_t <= 2^27 samples')
@@ -136,31 +120,16 @@ def track_climatology(lon, lat, vmax, groups, grid, thresholds=(), n_groups=None
     if n_trk and bool((~xp.isnan(vmax) & ~((vmax >= 0.0) & (vmax <= V_MAX))).any()):
         raise ValueError('vmax must be NaN or in [0, %g] m/s' % V_MAX)
     n_bin, shape = int(thr.size), (n_groups, grid.nlat, grid.nlon)
-
-    def new(shp, kind):
-        if torch_in:
-            return torch.empty(shp, dtype={'i4': torch.int32, 'i8': torch.int64, 'f8': torch.float64}[kind], device=dev)
-        return np.empty(shp, dtype=kind)
     res = dict(track=new(shape, 'i4'), exceed=new((n_groups, n_bin) + shape[1:], 'i4'), genesis=new(shape, 'i4'),
                lmi=new(shape, 'i4'), pdi=new(shape, 'i8'), genesis_k=new((n_trk,), 'i4'), lmi_v=new((n_trk,), 'f8'),
                lmi_k=new((n_trk,), 'i4'), pdi_storm=new((n_trk,), 'i8'))
-    gi = torch.as_tensor(g.astype(np.int32), device=dev) if torch_in else np.ascontiguousarray(g.astype(np.int32))
-    ptr = (lambda a: a.data_ptr()) if torch_in else (lambda a: a.ctypes.data)
+    gi = xp.as_tensor(g.astype(np.int32), device=fl.dev) if fl.torch else np.ascontiguousarray(g.astype(np.int32))
     out = _lib.ClimOut(**{k: (ptr(v) if k != 'exceed' or n_bin else None) for k, v in res.items()})
     trk = _lib.HazardTracks(n_trk=n_trk, n_t=n_t, row_stride=n_t, lon=ptr(lon), lat=ptr(lat), vmax=ptr(vmax), n_group=0,
                             group_off=None)
     cg = grid._c()
-    ctx = _Context(engine, device)
-    try:
-        args = (ctx.h, C.byref(trk), ptr(gi), n_groups, C.byref(cg), n_bin, thr.ctypes.data_as(_lib.DP), C.byref(out))
-        if torch_in:
-            ctx.check(ctx.L.tcr_climatology_dev(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        else:
-            ctx.check(ctx.L.tcr_climatology_host(*args))
-    finally:
-        if torch_in and ctx.own:
-            torch.cuda.current_stream(dev).synchronize()       # the context's workspace goes with it
-        ctx.close()
+    with fl.context(engine, device) as ctx:
+        ctx.call('tcr_climatology', C.byref(trk), ptr(gi), n_groups, C.byref(cg), n_bin, thr.ctypes.data_as(_lib.DP), C.byref(out))
     res['thresholds'] = thr
     return res
 
@@ -237,7 +206,7 @@ def _threshold_list(text):
     if text.strip().lower() == 'none':
         return np.zeros(0)
     if ':' in text:
-        thr = hazard._range(text, '--thresholds')
+        thr = analysis.parse_range(text, '--thresholds')
     else:
         try:
             thr = np.array([float(x) for x in text.split(',')])
@@ -253,43 +222,22 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(prog='python -m tropical_cyclone_risk_amd.climatology',
                                 description='Track, exceedance, genesis and LMI density, PDI, seasonal cycle and LMI distribution '
                                             'of track files.')
-    p.add_argument('tracks', nargs='+', help='track files (ensemble members); every year of every file is one group')
     p.add_argument('--cells', type=_cells, default=CellGrid.from_bounds(0.0, 360.0, -90.0, 90.0, 1.0),
                    metavar='LON0:LON1:D,LAT0:LAT1:D', help='the cell grid (default: the 1-degree globe)')
     p.add_argument('--thresholds', type=_threshold_list, default=np.array(SAFFIR_SIMPSON), metavar='LO:HI:STEP|V1,V2,..|none',
                    help='vmax thresholds of the exceedance maps in m/s (default: Saffir-Simpson categories 1-5)')
-    p.add_argument('--lmi-bins', type=lambda t: hazard._range(t, '--lmi-bins'), default=np.arange(0.0, 91.0, 5.0),
+    p.add_argument('--lmi-bins', type=lambda t: analysis.parse_range(t, '--lmi-bins'), default=np.arange(0.0, 91.0, 5.0),
                    metavar='LO:HI:STEP', help='edges of the LMI histogram in m/s (default 0:90:5)')
     p.add_argument('--basin', default=None, help="seasonal cycle of the storms of this basin only (the file's tc_basins)")
     p.add_argument('--per-group', action='store_true', help='maps per (file, year) group instead of summed over groups')
-    p.add_argument('--out', default='climatology.npz')
-    p.add_argument('--device', type=int, default=0)
+    analysis.add_track_args(p, 'climatology.npz')
     return p.parse_args(argv)
-
-
-def sample_spacing(times):
-    """dt (s) of the track files' `time` axes (one array per file): time[1] - time[0], uniform to a relative 1e-9 and equal in
-    every file; a file of one sample takes the namelist's output interval."""
-    from . import namelist
-    dts = []
-    for t in times:
-        t = np.asarray(t, dtype=np.float64).reshape(-1)
-        if t.size < 2:
-            dts.append(float(namelist.output_interval_s))
-            continue
-        dt = float(t[1] - t[0])
-        if not dt > 0 or np.any(np.abs(np.diff(t) - dt) > 1e-9 * dt):
-            raise ValueError('the time axis of a track file is not uniform')
-        dts.append(dt)
-    if any(abs(d - dts[0]) > 1e-9 * dts[0] for d in dts):
-        raise ValueError('the track files have different sample spacings: %s' % sorted(set(dts)))
-    return dts[0]
 
 
 def main(argv=None):
     args = parse_args(argv)
     grid = args.cells
-    lon, lat, vmax, groups, gfile, gyear, more = hazard.load_groups(args.tracks, extra=('tc_month', 'tc_basins', 'time'))
+    lon, lat, vmax, groups, gfile, gyear, more = analysis.load_groups(args.tracks, extra=('tc_month', 'tc_basins', 'time'))
     n_groups = len(gfile)
     dt = sample_spacing(more['time'])
     tc_month = np.concatenate([np.asarray(m, dtype=np.float64).reshape(-1) for m in more['tc_month']])
@@ -304,8 +252,8 @@ def main(argv=None):
     out.update(series)
     out.update(thresholds=r['thresholds'], lmi_bins=args.lmi_bins, lon_edges=grid.lon_edges, lat_edges=grid.lat_edges,
                cells=np.array([grid.lon0, grid.dlon, grid.nlon, grid.lat0, grid.dlat, grid.nlat], dtype=np.float64),
-               dt=dt, q_scale=Q_SCALE, per_group=args.per_group, groups=groups, group_file=gfile, group_year=gyear,
-               basin=str(args.basin or ''), files=np.array([str(f) for f in args.tracks]))
+               dt=dt, q_scale=Q_SCALE, per_group=args.per_group, groups=groups, basin=str(args.basin or ''),
+               **analysis.group_meta(args.tracks, gfile, gyear))
     np.savez(args.out, **out)
     n = series['n_storms']
     track = np.asarray(out['track'])

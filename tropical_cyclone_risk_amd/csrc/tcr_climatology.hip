@@ -286,10 +286,9 @@ int tcr_climatology_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, const int32_t
     if (clim_check(ctx, t, group, n_group, gr, n_bin, thresholds, o)) return -1;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
-    const size_t plane = (size_t)t->n_trk * t->row_stride, n_trk = (size_t)t->n_trk;
+    const size_t n_trk = (size_t)t->n_trk;
     const size_t n_map = (size_t)n_group * (size_t)(gr->nlon * gr->nlat), n_ex = n_map * (size_t)n_bin;
-    tcr_hazard_tracks d = *t;
-    d.lon = B.put(t->lon, plane); d.lat = B.put(t->lat, plane); d.vmax = B.put(t->vmax, plane);
+    tcr_hazard_tracks d;
     const int32_t *d_group = B.put(group, n_trk);
     tcr_clim_out dout{};
     dout.track = B.get<int32_t>(n_map); dout.genesis = B.get<int32_t>(n_map); dout.lmi = B.get<int32_t>(n_map);
@@ -297,7 +296,7 @@ int tcr_climatology_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, const int32_t
     dout.exceed = n_bin > 0 ? B.get<int32_t>(n_ex) : nullptr;
     dout.genesis_k = B.get<int32_t>(n_trk); dout.lmi_v = B.get<double>(n_trk); dout.lmi_k = B.get<int32_t>(n_trk);
     dout.pdi_storm = B.get<int64_t>(n_trk);
-    const bool ok = d.lon && d.lat && d.vmax && d_group && dout.track && dout.genesis && dout.lmi && dout.pdi &&
+    const bool ok = hazard_tracks_upload(B, t, &d) && d_group && dout.track && dout.genesis && dout.lmi && dout.pdi &&
                     (n_bin == 0 || dout.exceed) && dout.genesis_k && dout.lmi_v && dout.lmi_k && dout.pdi_storm;
     if (!ok) return fail(ctx, "tcr_climatology_host: device allocation / upload failed");
     if (tcr_climatology_dev(ctx, &d, d_group, n_group, gr, n_bin, thresholds, &dout, ctx->stream)) return -1;

@@ -83,6 +83,16 @@ int hazard_check(tcr_ctx *ctx, const tcr_hazard_tracks *t, int64_t n_site, const
     return scan_check(ctx, "tcr_hazard", t, INT64_MAX, "n_t >= 1", n_site, n_bin, thr);
 }
 
+// For a _host entry point on tcr_hazard_tracks: *d = *t with the three planes on the device (B owns them).  No storms: nothing is
+// read.  false: allocation or upload failed.
+bool hazard_tracks_upload(DevBuf &B, const tcr_hazard_tracks *t, tcr_hazard_tracks *d)
+{
+    auto up = [&](const double *p) { return t->n_trk > 0 ? B.put(p, (size_t)t->n_trk * t->row_stride) : B.get<double>(1); };
+    *d = *t;
+    d->lon = up(t->lon); d->lat = up(t->lat); d->vmax = up(t->vmax);
+    return d->lon && d->lat && d->vmax;
+}
+
 }  // namespace
 
 extern "C" {
@@ -97,11 +107,7 @@ int tcr_hazard_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, int64_t n_site, con
     return scan_run<HzSample>(ctx, ctx->hz, "tcr_hazard", t, t->n_t, 0, n_site, site_lon, site_lat, radius_km, kHzRe, n_bin, thresholds,
                               counts, site_max, st, [&](const ScanArgs<HzSample> &m, void *, dim3 grid, size_t lds) {
         HzPrepArgs p{t->lon, t->lat, t->vmax, t->n_trk, t->n_t, t->row_stride, m.rows};
-        hipLaunchKernelGGL(k_hazard_prep, dim3((unsigned)t->n_trk), dim3(64), 0, st, p);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_site_scan<HazardScan>, grid, dim3(64), lds, st, m, HazardScan{});
-        return hipGetLastError();
+        return scan_launch(k_hazard_prep, p, t->n_trk, m, grid, lds, st, HazardScan{});
     });
 }
 
@@ -112,11 +118,9 @@ int tcr_hazard_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, int64_t n_site, co
     if (hazard_check(ctx, t, n_site, site_lon, site_lat, radius_km, n_bin, thresholds, counts)) return -1;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
-    const size_t plane = (size_t)std::max<int64_t>(1, t->n_trk * t->row_stride);
-    tcr_hazard_tracks d = *t;
-    d.lon = B.put(t->lon, plane); d.lat = B.put(t->lat, plane); d.vmax = B.put(t->vmax, plane);
+    tcr_hazard_tracks d;
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, n_bin, site_max != nullptr);
-    if (!d.lon || !d.lat || !d.vmax || !io.ok) return fail(ctx, "tcr_hazard_host: device allocation / upload failed");
+    if (!hazard_tracks_upload(B, t, &d) || !io.ok) return fail(ctx, "tcr_hazard_host: device allocation / upload failed");
     if (tcr_hazard_dev(ctx, &d, n_site, io.site_lon, io.site_lat, radius_km, n_bin, thresholds, io.counts, io.site_max, ctx->stream)) return -1;
     return scan_download(ctx, io, counts, site_max);
 }

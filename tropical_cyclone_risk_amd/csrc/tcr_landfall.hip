@@ -242,15 +242,14 @@ int tcr_landfall_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, int32_t max_even
     if (t->n_trk == 0) return 0;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
-    const size_t plane = (size_t)t->n_trk * t->row_stride, n_ev = (size_t)t->n_trk * max_events, n_fl = (size_t)t->n_trk * t->n_t;
-    tcr_hazard_tracks d = *t;
-    d.lon = B.put(t->lon, plane); d.lat = B.put(t->lat, plane); d.vmax = B.put(t->vmax, plane);
+    const size_t n_ev = (size_t)t->n_trk * max_events, n_fl = (size_t)t->n_trk * t->n_t;
+    tcr_hazard_tracks d;
     int32_t *d_n = B.get<int32_t>((size_t)t->n_trk);
     int32_t *d_k = n_ev ? B.get<int32_t>(n_ev) : nullptr;
     double *d_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     for (double *&p : d_ev) if (n_ev) p = B.get<double>(n_ev);
     uint8_t *d_fl = flags ? B.get<uint8_t>(n_fl) : nullptr;
-    bool ok = d.lon && d.lat && d.vmax && d_n && (!flags || d_fl);
+    bool ok = hazard_tracks_upload(B, t, &d) && d_n && (!flags || d_fl);
     if (n_ev) ok = ok && d_k && d_ev[0] && d_ev[1] && d_ev[2] && d_ev[3];
     if (!ok) return fail(ctx, "tcr_landfall_host: device allocation / upload failed");
     if (tcr_landfall_dev(ctx, &d, max_events, d_n, d_k, d_ev[0], d_ev[1], d_ev[2], d_ev[3], d_fl, ctx->stream)) return -1;

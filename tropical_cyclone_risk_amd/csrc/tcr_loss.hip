@@ -130,18 +130,11 @@ int tcr_loss_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params *
     const int rc = scan_run<WfRec>(ctx, w, "tcr_loss", t, n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat, prm->r_out_km,
                                    kWfEarthR / 1000.0, n_bin, thresholds, counts, nullptr, st,
                                    [&](const ScanArgs<WfRec> &m, void *stage, dim3 grid, size_t lds) {
-        WfPrepArgs p{t->lon, t->lat, t->v, t->u250, t->v250, t->u850, t->v850, t->rmax_km, t->n_trk, t->n_t, t->row_stride,
-                     prm->dt_s, prm->rmax_const_km, prm->substeps, static_cast<WfStage *>(stage), m.rows};
-        hipLaunchKernelGGL(k_wind_prep, dim3((unsigned)t->n_trk), dim3(64), 0, st, p);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
         if (c == 1.0)
-            hipLaunchKernelGGL(k_site_scan<LossScan<true>>, grid, dim3(64), lds, st, m,
-                               LossScan<true>{{c, 2.0 - c, 1.0 / (2.0 - c)}, site_value, site_v_half, lp->v_thresh, lp->v_half, tile_loss, site_part});
-        else
-            hipLaunchKernelGGL(k_site_scan<LossScan<false>>, grid, dim3(64), lds, st, m,
-                               LossScan<false>{{c, 2.0 - c, 1.0 / (2.0 - c)}, site_value, site_v_half, lp->v_thresh, lp->v_half, tile_loss, site_part});
-        return hipGetLastError();
+            return wind_scan_launch(t, prm, m, stage, grid, lds, st,
+                                    LossScan<true>{{c, 2.0 - c, 1.0 / (2.0 - c)}, site_value, site_v_half, lp->v_thresh, lp->v_half, tile_loss, site_part});
+        return wind_scan_launch(t, prm, m, stage, grid, lds, st,
+                                LossScan<false>{{c, 2.0 - c, 1.0 / (2.0 - c)}, site_value, site_v_half, lp->v_thresh, lp->v_half, tile_loss, site_part});
     });
     if (rc) return rc;
     const int64_t *d_tab = static_cast<const int64_t *>(w.d[4]);
@@ -171,20 +164,14 @@ int tcr_loss_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params 
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
-    const size_t plane = (size_t)std::max<int64_t>(1, t->n_trk * t->row_stride);
-    tcr_wind_tracks d = *t;
-    auto up = [&](const double *p) { return t->n_trk > 0 ? B.put(p, plane) : B.get<double>(1); };   // (no storms: nothing to read)
-    d.lon = up(t->lon); d.lat = up(t->lat); d.v = up(t->v);
-    d.u250 = up(t->u250); d.v250 = up(t->v250); d.u850 = up(t->u850); d.v850 = up(t->v850);
-    d.rmax_km = t->rmax_km ? up(t->rmax_km) : nullptr;
+    tcr_wind_tracks d;
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, n_bin, false);
     const double *d_value = B.put(site_value, (size_t)n_site);
     const double *d_vhalf = site_v_half ? B.put(site_v_half, (size_t)n_site) : nullptr;
     double *d_event = B.get<double>((size_t)std::max<int64_t>(1, t->n_trk));
     double *d_agg = B.get<double>((size_t)t->n_group), *d_max = B.get<double>((size_t)t->n_group);
     double *d_site = B.get<double>((size_t)n_site);
-    if (!d.lon || !d.lat || !d.v || !d.u250 || !d.v250 || !d.u850 || !d.v850 || (t->rmax_km && !d.rmax_km) || !io.ok || !d_value ||
-        (site_v_half && !d_vhalf) || !d_event || !d_agg || !d_max || !d_site)
+    if (!wind_tracks_upload(B, t, &d) || !io.ok || !d_value || (site_v_half && !d_vhalf) || !d_event || !d_agg || !d_max || !d_site)
         return fail(ctx, "tcr_loss_host: device allocation / upload failed");
     if (tcr_loss_dev(ctx, &d, prm, lp, n_site, io.site_lon, io.site_lat, d_value, d_vhalf, n_bin, thresholds, io.counts, d_event, d_agg,
                      d_max, d_site, ctx->stream))

@@ -352,6 +352,18 @@ int scan_run(tcr_ctx *ctx, ScanWs &w, const char *who, const Tracks *t, int64_t 
     return 0;
 }
 
+// What a launch step enqueues: the analysis's prep kernel (one block of 64 lanes per storm) on p, then Policy's scan.
+template <class Policy, class PrepArgs>
+hipError_t scan_launch(void (*prep)(PrepArgs), const PrepArgs &p, int64_t n_trk, const ScanArgs<typename Policy::Rec> &m, dim3 grid,
+                       size_t lds, hipStream_t st, const Policy &pol)
+{
+    hipLaunchKernelGGL(prep, dim3((unsigned)n_trk), dim3(64), 0, st, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_site_scan<Policy>, grid, dim3(64), lds, st, m, pol);
+    return hipGetLastError();
+}
+
 // the sites and outputs of a _host entry point on the device (buffers of B), and the way back
 struct ScanHostIO {
     const double *site_lon, *site_lat;

@@ -206,6 +206,28 @@ int windfield_check(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_param
     return scan_check(ctx, "tcr_windfield", t, 1 << 20, "1 <= n_t <= 2^20", n_site, n_bin, thr);
 }
 
+// The launch step of scan_run for every analysis on the footprint's records: the footprint's prep kernel, then Policy's scan.
+template <typename Policy>
+hipError_t wind_scan_launch(const tcr_wind_tracks *t, const tcr_wind_params *prm, const ScanArgs<WfRec> &m, void *stage, dim3 grid,
+                            size_t lds, hipStream_t st, const Policy &pol)
+{
+    WfPrepArgs p{t->lon, t->lat, t->v, t->u250, t->v250, t->u850, t->v850, t->rmax_km, t->n_trk, t->n_t, t->row_stride,
+                 prm->dt_s, prm->rmax_const_km, prm->substeps, static_cast<WfStage *>(stage), m.rows};
+    return scan_launch(k_wind_prep, p, t->n_trk, m, grid, lds, st, pol);
+}
+
+// For a _host entry point on tcr_wind_tracks: *d = *t with the seven planes (eight with rmax_km) on the device (B owns them).  No
+// storms: nothing is read.  false: allocation or upload failed.
+bool wind_tracks_upload(DevBuf &B, const tcr_wind_tracks *t, tcr_wind_tracks *d)
+{
+    auto up = [&](const double *p) { return t->n_trk > 0 ? B.put(p, (size_t)t->n_trk * t->row_stride) : B.get<double>(1); };
+    *d = *t;
+    d->lon = up(t->lon); d->lat = up(t->lat); d->v = up(t->v);
+    d->u250 = up(t->u250); d->v250 = up(t->v250); d->u850 = up(t->u850); d->v850 = up(t->v850);
+    d->rmax_km = t->rmax_km ? up(t->rmax_km) : nullptr;
+    return d->lon && d->lat && d->v && d->u250 && d->v250 && d->u850 && d->v850 && (!t->rmax_km || d->rmax_km);
+}
+
 }  // namespace
 
 extern "C" {
@@ -223,14 +245,8 @@ int tcr_windfield_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_par
     return scan_run<WfRec>(ctx, ctx->wf, "tcr_windfield", t, n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat, prm->r_out_km,
                            kWfEarthR / 1000.0, n_bin, thresholds, counts, site_max, st,
                            [&](const ScanArgs<WfRec> &m, void *stage, dim3 grid, size_t lds) {
-        WfPrepArgs p{t->lon, t->lat, t->v, t->u250, t->v250, t->u850, t->v850, t->rmax_km, t->n_trk, t->n_t, t->row_stride,
-                     prm->dt_s, prm->rmax_const_km, prm->substeps, static_cast<WfStage *>(stage), m.rows};
-        hipLaunchKernelGGL(k_wind_prep, dim3((unsigned)t->n_trk), dim3(64), 0, st, p);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (c == 1.0) hipLaunchKernelGGL(k_site_scan<WindScan<true>>, grid, dim3(64), lds, st, m, WindScan<true>{c, 2.0 - c, 1.0 / (2.0 - c)});
-        else hipLaunchKernelGGL(k_site_scan<WindScan<false>>, grid, dim3(64), lds, st, m, WindScan<false>{c, 2.0 - c, 1.0 / (2.0 - c)});
-        return hipGetLastError();
+        if (c == 1.0) return wind_scan_launch(t, prm, m, stage, grid, lds, st, WindScan<true>{c, 2.0 - c, 1.0 / (2.0 - c)});
+        return wind_scan_launch(t, prm, m, stage, grid, lds, st, WindScan<false>{c, 2.0 - c, 1.0 / (2.0 - c)});
     });
 }
 
@@ -258,14 +274,9 @@ int tcr_windfield_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_pa
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
-    const size_t plane = (size_t)std::max<int64_t>(1, t->n_trk * t->row_stride);
-    tcr_wind_tracks d = *t;
-    d.lon = B.put(t->lon, plane); d.lat = B.put(t->lat, plane); d.v = B.put(t->v, plane);
-    d.u250 = B.put(t->u250, plane); d.v250 = B.put(t->v250, plane); d.u850 = B.put(t->u850, plane); d.v850 = B.put(t->v850, plane);
-    d.rmax_km = t->rmax_km ? B.put(t->rmax_km, plane) : nullptr;
+    tcr_wind_tracks d;
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, n_bin, site_max != nullptr);
-    if (!d.lon || !d.lat || !d.v || !d.u250 || !d.v250 || !d.u850 || !d.v850 || (t->rmax_km && !d.rmax_km) || !io.ok)
-        return fail(ctx, "tcr_windfield_host: device allocation / upload failed");
+    if (!wind_tracks_upload(B, t, &d) || !io.ok) return fail(ctx, "tcr_windfield_host: device allocation / upload failed");
     if (tcr_windfield_dev(ctx, &d, prm, n_site, io.site_lon, io.site_lat, n_bin, thresholds, io.counts, io.site_max, ctx->stream)) return -1;
     return scan_download(ctx, io, counts, site_max);
 }

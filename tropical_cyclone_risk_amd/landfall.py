@@ -20,8 +20,8 @@ import weakref
 
 import numpy as np
 
-from . import _lib, hazard
-from .hazard import DEFAULT_THRESHOLDS, _Context, _is_tensor
+from . import _lib, analysis, hazard
+from .analysis import DEFAULT_THRESHOLDS, to_numpy as _np
 
 EVENT_FIELDS = ('lon', 'lat', 'v_landfall', 'v_inland')
 _FIRST_CAPACITY = 8
@@ -78,52 +78,30 @@ def detect_landfalls(lon, lat, vmax, land_grid, engine=None, device=0, return_fl
     ``engine``: a TCEngine whose context is used (None: one is opened for the call).
     """
     grid = land_grid if isinstance(land_grid, LandGrid) else LandGrid(*land_grid)
-    torch_in = _is_tensor(lon)
-    if torch_in:
-        import torch
-        dev = lon.device
-        lon, lat, vmax = (torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous() for a in (lon, lat, vmax))
-        device = dev.index if dev.index is not None else torch.cuda.current_device()
-    else:
-        lon, lat, vmax = (np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in (lon, lat, vmax))
-    if lon.ndim != 2 or tuple(lat.shape) != tuple(lon.shape) or tuple(vmax.shape) != tuple(lon.shape):
-        raise ValueError('lon, lat and vmax must be [n_trk][n_t] arrays of one shape')
+    (lon, lat, vmax), fl = analysis.as_planes((lon, lat, vmax), 'lon, lat and vmax')
+    lon, lat, vmax = (fl.contiguous(a) for a in (lon, lat, vmax))
     n_trk, n_t = int(lon.shape[0]), int(lon.shape[1])
     if n_t < 1:
         raise ValueError('the tracks need at least one sample')
-
-    def new(shape, kind):
-        if torch_in:
-            dt = {'i4': torch.int32, 'f8': torch.float64, 'u1': torch.uint8}[kind]
-            return torch.empty(shape, dtype=dt, device=dev)
-        return np.empty(shape, dtype=kind)
-    ptr = (lambda a: a.data_ptr()) if torch_in else (lambda a: a.ctypes.data)
+    new, ptr = fl.new, fl.ptr
     trk = _lib.HazardTracks(n_trk=n_trk, n_t=n_t, row_stride=n_t, lon=ptr(lon), lat=ptr(lat), vmax=ptr(vmax), n_group=0,
                             group_off=None)
     n_lf = new((n_trk,), 'i4')
     flags = new((n_trk, n_t), 'u1') if return_flags else None
-    ctx = _Context(engine, device)
-    try:
+    with fl.context(engine, device) as ctx:
         _upload(ctx, grid, engine)
 
-        def run(cap, fl):
+        def run(cap, flag_buf):
             k = new((n_trk, cap), 'i4')
             planes = [new((n_trk, cap), 'f8') for _ in EVENT_FIELDS]
-            args = [ctx.h, C.byref(trk), cap, ptr(n_lf), ptr(k)] + [ptr(p) for p in planes] + [ptr(fl) if fl is not None else None]
             if n_trk:
-                if torch_in:
-                    ctx.check(ctx.L.tcr_landfall_dev(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-                else:
-                    ctx.check(ctx.L.tcr_landfall_host(*args))
+                ctx.call('tcr_landfall', C.byref(trk), cap, ptr(n_lf), ptr(k), *[ptr(p) for p in planes],
+                         ptr(flag_buf) if flag_buf is not None else None)
             return k, planes
         k, planes = run(_FIRST_CAPACITY, flags)
         n_max = int(n_lf.max()) if n_trk else 0             # (a device tensor: waits for the call)
         if n_max > _FIRST_CAPACITY:
             k, planes = run(n_max, None)
-    finally:
-        if torch_in and ctx.own:
-            torch.cuda.current_stream(dev).synchronize()       # the context's land grid goes with it
-        ctx.close()
     res = dict(n_landfall=n_lf, k=k[:, :n_max])
     for name, p in zip(EVENT_FIELDS, planes):
         res[name] = p[:, :n_max]
@@ -133,10 +111,6 @@ def detect_landfalls(lon, lat, vmax, land_grid, engine=None, device=0, return_fl
 
 
 # ---------------------------------------------------------------------------------------------------------- aggregates
-def _np(a):
-    return np.asarray(a.cpu() if _is_tensor(a) else a)
-
-
 def in_box(lon, lat, box):
     """lon0 <= lon <= lon1 along the circle (the box may cross the dateline; either longitude convention) and
     lat0 <= lat <= lat1.  box = (lon0, lon1, lat0, lat1).  NaN is outside."""
@@ -190,14 +164,7 @@ def landfall_counts(events, groups, thresholds=DEFAULT_THRESHOLDS, regions=None,
     v = _np(events['v_landfall']).astype(np.float64)
     elon, elat = _np(events['lon']).astype(np.float64), _np(events['lat']).astype(np.float64)
     live = _np(events['k']) >= 0
-    g = _np(groups).reshape(-1)
-    n_trk = v.shape[0]
-    if g.shape[0] != n_trk or (n_trk and (g.dtype.kind not in 'iu' or g.min() < 0)):
-        raise ValueError('groups must hold one non-negative integer per storm')
-    g = g.astype(np.int64)
-    n_groups = int(n_groups if n_groups is not None else (g.max() + 1 if n_trk else 1))
-    if n_trk and g.max() >= n_groups:
-        raise ValueError('a group index is >= n_groups')
+    g, n_groups = analysis.group_index(groups, v.shape[0], n_groups)
     first, mx, has = _first_and_max(v, live)
     c_first, c_max, n_st = _storm_counts(first, mx, has, g, n_groups, thr)
     res = dict(first=c_first, max=c_max, n_storms=n_st, thresholds=thr)
@@ -224,7 +191,7 @@ def landfall_site_hazard(events, groups, site_lon, site_lat, radius_km=100., thr
     device tensors as events everything stays there."""
     planes = [events['lon'], events['lat'], events['v_landfall']]
     if int(planes[0].shape[1]) == 0:                       # no storm made landfall: one empty (NaN) event column
-        if _is_tensor(planes[0]):
+        if analysis.is_tensor(planes[0]):
             import torch
             planes = [torch.full((int(p.shape[0]), 1), float('nan'), dtype=torch.float64, device=p.device) for p in planes]
         else:
@@ -251,32 +218,26 @@ def _region(text):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog='python -m tropical_cyclone_risk_amd.landfall',
                                 description='Landfall events, landfall intensity exceedance counts and return periods of track files.')
-    p.add_argument('tracks', nargs='+', help='track files (ensemble members); every year of every file is one group')
     p.add_argument('--land', required=True, metavar='land.nc', help="the model's land mask (intensity/data/land.nc schema)")
-    p.add_argument('--site', type=hazard._site, action='append', default=[], metavar='LON,LAT',
-                   help='repeatable; write --site=LON,LAT when LON is negative')
-    p.add_argument('--sites', metavar='FILE.csv', help='one LON,LAT per line (lines that are not two numbers are skipped)')
-    p.add_argument('--grid', type=hazard._grid, metavar='LON0:LON1:DLON,LAT0:LAT1:DLAT')
+    analysis.add_site_args(p)
     p.add_argument('--region', type=_region, action='append', default=[], metavar='NAME=LON0:LON1,LAT0:LAT1',
                    help='repeatable; the box may cross the dateline (LON0 > LON1)')
     p.add_argument('--radius-km', type=float, default=100.0)
-    p.add_argument('--thresholds', type=lambda t: hazard._range(t, '--thresholds'), default=DEFAULT_THRESHOLDS,
-                   metavar='LO:HI:STEP')
-    p.add_argument('--out', default='landfall.npz')
-    p.add_argument('--device', type=int, default=0)
+    analysis.add_threshold_arg(p)
+    analysis.add_track_args(p, 'landfall.npz')
     return p.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
-    site_lon, site_lat = hazard.collect_sites(args)
-    lon, lat, vmax, groups, gfile, gyear = hazard.load_groups(args.tracks)
+    site_lon, site_lat = analysis.collect_sites(args)
+    lon, lat, vmax, groups, gfile, gyear = analysis.load_groups(args.tracks)
     total_years = len(gfile)
     grid = read_land(args.land)
     ev = detect_landfalls(lon, lat, vmax, grid, device=args.device)
     c = landfall_counts(ev, groups, args.thresholds, regions=args.region, n_groups=total_years)
     out = dict(n_landfall=ev['n_landfall'], event_k=ev['k'], thresholds=c['thresholds'], groups=groups, total_years=total_years,
-               group_file=gfile, group_year=gyear, files=np.array([str(f) for f in args.tracks]),
+               **analysis.group_meta(args.tracks, gfile, gyear),
                counts_first=c['first'], counts_max=c['max'], n_storms=c['n_storms'],
                return_period_first=hazard.return_periods(c['first'][None], total_years)[0],
                return_period_max=hazard.return_periods(c['max'][None], total_years)[0],

@@ -27,8 +27,9 @@ import sys
 
 import numpy as np
 
-from . import _lib, hazard, windfield
-from .hazard import _is_tensor
+from . import _lib, analysis, windfield
+from .analysis import DEFAULT_THRESHOLDS, to_numpy
+from .sitescan import site_scan
 
 V_THRESH, V_HALF = 25.7, 74.7          # m/s: CLIMADA's defaults of the Emanuel (2011) function
 DEFAULT_RETURN_PERIODS = (10.0, 25.0, 50.0, 100.0, 250.0)
@@ -44,7 +45,7 @@ def damage(m, v_thresh=V_THRESH, v_half=V_HALF):
 
 
 def portfolio_loss(lon, lat, v, env, groups, site_lon, site_lat, value, dt_s, v_thresh=V_THRESH, v_half=V_HALF, rmax_km=None,
-                   ck_cd=None, r_out_km=500., substeps=1, thresholds=hazard.DEFAULT_THRESHOLDS, engine=None, device=0,
+                   ck_cd=None, r_out_km=500., substeps=1, thresholds=DEFAULT_THRESHOLDS, engine=None, device=0,
                    n_groups=None):
     """Event losses, year losses, site losses and footprint exceedance counts of a portfolio.
 
@@ -56,10 +57,8 @@ def portfolio_loss(lon, lat, v, env, groups, site_lon, site_lat, value, dt_s, v_
     caller's site order, ``thresholds``; arrays in the type and on the device of ``lon``.  No sum uses atomics: a repeated call
     gives the same bits.
     """
-    planes, conv, thr, wprm = windfield._prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
-    xp = np
-    if _is_tensor(planes[0]):
-        import torch as xp
+    planes, fl, thr, wprm = windfield._prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
+    xp, conv = fl.xp, fl.conv
     v_thresh = float(v_thresh)
     if not (np.isfinite(v_thresh) and v_thresh >= 0):
         raise ValueError('v_thresh must be finite and >= 0')
@@ -70,7 +69,7 @@ def portfolio_loss(lon, lat, v, env, groups, site_lon, site_lat, value, dt_s, v_
     if not bool((xp.isfinite(value) & (value >= 0)).all()):
         raise ValueError('value must be finite and >= 0')
     vh_site = None
-    if np.ndim(v_half.cpu() if _is_tensor(v_half) else v_half) == 0:
+    if np.ndim(to_numpy(v_half)) == 0:
         vh0 = float(v_half)
         if not (np.isfinite(vh0) and vh0 > v_thresh):
             raise ValueError('v_half must be finite and > v_thresh')
@@ -83,23 +82,22 @@ def portfolio_loss(lon, lat, v, env, groups, site_lon, site_lat, value, dt_s, v_
         vh0 = float(vh_site.max()) if n_site else V_HALF      # (the scalar is not used, but it is checked)
     lprm = _lib.LossParams(v_thresh=v_thresh, v_half=vh0)
 
-    def make_args(tracks, sites, out, more):
-        (p_value, p_vhalf), outs = more
-        return (C.byref(windfield._tracks_struct(tracks)), C.byref(wprm), C.byref(lprm)) + sites + (p_value, p_vhalf) + out[:3] + \
-            tuple(outs)
-    return hazard._site_scan('tcr_loss', planes, conv, groups, n_groups, site_lon, site_lat, thr, False, engine, device, make_args,
-                             site_extras=(value, vh_site),
-                             more_outputs=(('event_loss', 'trk'), ('year_agg', 'group'), ('year_max', 'group'), ('site_loss', 'site')))
+    def make_args(a):
+        return (C.byref(windfield._tracks_struct(a)), C.byref(wprm), C.byref(lprm)) + a.sites + tuple(a.extras) + a.out[:3] + \
+            tuple(a.outputs)
+    return site_scan('tcr_loss', planes, fl, groups, n_groups, site_lon, site_lat, thr, False, engine, device, make_args,
+                     site_extras=(value, vh_site),
+                     more_outputs=(('event_loss', 'trk'), ('year_agg', 'group'), ('year_max', 'group'), ('site_loss', 'site')))
 
 
 def year_loss_table(event_loss, groups, n_groups):
     """(year_agg, year_max) [n_groups] of an event loss table in NumPy: the sum and the largest event loss of every group, 0 for
     a group without storms.  For callers who filter or rescale events first."""
-    e = np.asarray(event_loss.cpu() if _is_tensor(event_loss) else event_loss, dtype=np.float64).reshape(-1)
-    g = np.asarray(groups.cpu() if _is_tensor(groups) else groups).reshape(-1)
-    n_groups = int(n_groups)
-    if g.shape[0] != e.shape[0] or (e.size and (g.dtype.kind not in 'iu' or g.min() < 0 or g.max() >= n_groups)) or n_groups < 1:
-        raise ValueError('groups must hold one integer in [0, n_groups) per event')
+    e = to_numpy(event_loss).astype(np.float64).reshape(-1)
+    bad = 'groups must hold one integer in [0, n_groups) per event'
+    g, n_groups = analysis.group_index(groups, e.shape[0], int(n_groups), bad=bad, over=bad)
+    if n_groups < 1:
+        raise ValueError(bad)
     agg, mx = np.zeros(n_groups), np.zeros(n_groups)
     if e.size:
         np.add.at(agg, g, e)
@@ -112,7 +110,7 @@ def loss_curve(year_losses, total_years, return_periods=DEFAULT_RETURN_PERIODS):
     exceeded or equalled in k of total_years years has the return period total_years / k, hazard.return_periods' formula).
     NaN for T > total_years, the smallest year loss for T < 1; years beyond len(year_losses) count as 0.  year_agg gives the
     aggregate (AEP) curve, year_max the occurrence (OEP) curve."""
-    y = np.asarray(year_losses.cpu() if _is_tensor(year_losses) else year_losses, dtype=np.float64).reshape(-1)
+    y = to_numpy(year_losses).astype(np.float64).reshape(-1)
     total_years = int(total_years)
     if total_years < 1 or y.size > total_years:
         raise ValueError('total_years must be >= 1 and >= the number of year losses')
@@ -129,7 +127,7 @@ def loss_curve(year_losses, total_years, return_periods=DEFAULT_RETURN_PERIODS):
 
 def average_annual_loss(year_agg, total_years):
     """The sum of the year losses over total_years (years beyond len(year_agg) count as 0)."""
-    y = np.asarray(year_agg.cpu() if _is_tensor(year_agg) else year_agg, dtype=np.float64)
+    y = to_numpy(year_agg).astype(np.float64)
     return float(y.sum() / float(total_years))
 
 
@@ -147,18 +145,13 @@ def _periods(text):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog='python -m tropical_cyclone_risk_amd.loss',
                                 description='Event, year and site losses and AEP / OEP loss curves of track files for an exposure.')
-    p.add_argument('tracks', nargs='+', help='track files (ensemble members); every year of every file is one group')
     p.add_argument('--exposure', required=True, metavar='FILE.csv',
                    help='one LON,LAT,VALUE[,V_HALF] per line (lines that are not numbers are skipped)')
     p.add_argument('--v-thresh', type=float, default=V_THRESH, help='wind below which nothing is damaged (m/s)')
     p.add_argument('--v-half', type=float, default=V_HALF, help='wind of half damage (m/s) where the exposure gives none')
-    p.add_argument('--rmax-km', type=float, default=None, help='constant radius of maximum wind (default: Willoughby et al. 2006)')
-    p.add_argument('--r-out-km', type=float, default=500.0)
-    p.add_argument('--substeps', type=int, default=1, help='evaluation points per sample interval (1 = the samples only)')
-    p.add_argument('--ck-cd', type=float, default=None, help='Ck / Cd of the profile (default: the namelist\'s)')
+    analysis.add_footprint_args(p)
     p.add_argument('--return-periods', type=_periods, default=np.array(DEFAULT_RETURN_PERIODS), metavar='T1,T2,...')
-    p.add_argument('--out', default='loss.npz')
-    p.add_argument('--device', type=int, default=0)
+    analysis.add_track_args(p, 'loss.npz')
     return p.parse_args(argv)
 
 
@@ -182,15 +175,12 @@ def read_exposure_csv(fn, v_half=V_HALF):
 
 
 def main(argv=None):
-    from .climatology import sample_spacing
     args = parse_args(argv)
     site_lon, site_lat, value, vh, any_vh = read_exposure_csv(args.exposure, args.v_half)
     if site_lon.size == 0:
         raise SystemExit('no exposure')
-    lon, lat, _, groups, gfile, gyear, more = hazard.load_groups(args.tracks, extra=('v_trks',) + windfield.ENV_VARS + ('time',))
+    lon, lat, _, v, env, groups, gfile, gyear, dt = analysis.load_wind_planes(args.tracks)
     total_years = len(gfile)
-    dt = sample_spacing(more['time'])
-    v, *env = (np.concatenate([np.asarray(a, dtype=np.float64) for a in more[k]]) for k in ('v_trks',) + windfield.ENV_VARS)
     res = portfolio_loss(lon, lat, v, env, groups, site_lon, site_lat, value, dt, v_thresh=args.v_thresh,
                          v_half=vh if any_vh else args.v_half, rmax_km=args.rmax_km, ck_cd=args.ck_cd, r_out_km=args.r_out_km,
                          substeps=args.substeps, device=args.device, n_groups=total_years)
@@ -201,8 +191,8 @@ def main(argv=None):
              loss_cost=res['site_loss'] / total_years, counts=res['counts'], thresholds=res['thresholds'], aal=aal,
              return_periods=T, aep=aep, oep=oep, site_lon=site_lon, site_lat=site_lat, value=value, v_half=vh,
              v_thresh=args.v_thresh, total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps,
-             rmax_km=np.nan if args.rmax_km is None else args.rmax_km, dt_s=dt, group_file=gfile, group_year=gyear,
-             files=np.array([str(f) for f in args.tracks]))
+             rmax_km=np.nan if args.rmax_km is None else args.rmax_km, dt_s=dt,
+             **analysis.group_meta(args.tracks, gfile, gyear))
     print('%d sites (total value %g), %d storms, %d groups (%d files), total_years = %d, r_out = %g km, %d substeps -> %s'
           % (site_lon.size, value.sum(), lon.shape[0], total_years, len(args.tracks), total_years, args.r_out_km, args.substeps,
              args.out))

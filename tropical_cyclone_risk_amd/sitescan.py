@@ -1,0 +1,104 @@
+"""The Python side of the per-site scan (csrc/tcr_sitescan.h), which site hazard, wind footprint and portfolio loss share: the
+checks of sites and groups, the order the kernel wants (the storms of a group next to each other, the sites in Z-order), the
+call, and the way back to the caller's site and storm order."""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .analysis import group_index
+
+# What site_scan hands an analysis's make_args, ready to pass on: ``tracks``, the fields every tracks struct has (n_trk, n_t,
+# row_stride, n_group, group_off) as keywords; ``planes``, the pointers of the permuted planes; ``sites`` = (n_site, lon, lat);
+# ``out`` = (n_bin, thresholds, counts, site_max); ``extras``, the pointers of the per-site extras (None stays None) and
+# ``outputs``, those of the extra outputs (both empty when the analysis names none).
+ScanArgs = collections.namedtuple('ScanArgs', 'tracks planes sites out extras outputs')
+
+
+def spatial_order(lon, lat, xp):
+    """Z-order (Morton) of the sites on a 2^16 x 2^16 lon / lat raster: runs of consecutive sites are compact patches, which
+    is what the kernel's per-64-site culling wants.  `xp` is numpy or torch (the same integer operations on both)."""
+    to_int = (lambda a: a.astype(np.int64)) if xp is np else (lambda a: a.long())
+    qx = to_int((lon % 360.0) * (65535.0 / 360.0))
+    qy = to_int((lat + 90.0).clip(0.0, 180.0) * (65535.0 / 180.0))
+
+    def spread(v):
+        v = (v | (v << 8)) & 0x00FF00FF
+        v = (v | (v << 4)) & 0x0F0F0F0F
+        v = (v | (v << 2)) & 0x33333333
+        return (v | (v << 1)) & 0x55555555
+    key = spread(qx) | (spread(qy) << 1)
+    return xp.argsort(key, stable=True) if xp is not np else np.argsort(key, kind='stable')
+
+
+def site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device, make_args,
+              site_extras=(), more_outputs=()):
+    """Checks the sites and groups, puts the storms of a group next to each other and the sites in spatial order, runs
+    ``entry + '_dev'`` (torch tensors, on the current stream) or ``entry + '_host'`` (NumPy) and returns ``counts``,
+    ``thresholds`` and with return_max ``site_max`` in the caller's site and storm order.  planes, fl: of analysis.as_planes.
+    make_args(ScanArgs) -> the entry point's arguments after the context.  The library is not touched before every check here has
+    passed.
+
+    site_extras: further [n_site] inputs (or None), which go through the site permutation with the coordinates.  more_outputs:
+    (name, axis) pairs of fp64 outputs along 'trk', 'group' or 'site', which come back under their names in the caller's order."""
+    xp = fl.xp
+    site_lon, site_lat = (fl.conv(a).reshape(-1) for a in (site_lon, site_lat))
+    if site_lon.shape[0] != site_lat.shape[0] or site_lon.shape[0] < 1:
+        raise ValueError('site_lon and site_lat must be non-empty and of one length')
+    if not bool(xp.isfinite(site_lon).all()) or not bool(xp.isfinite(site_lat).all()):
+        raise ValueError('site coordinates must be finite')
+    site_extras = [None if a is None else fl.conv(a).reshape(-1) for a in site_extras]
+    if any(a is not None and a.shape[0] != site_lon.shape[0] for a in site_extras):
+        raise ValueError('a per-site array must hold one value per site')
+    n_trk, n_t = int(planes[0].shape[0]), int(planes[0].shape[1])
+    g, n_groups = group_index(groups, n_trk, n_groups)
+
+    # storms grouped contiguously (stable: storms keep their order inside a group), sites in spatial order
+    order = np.argsort(g, kind='stable')
+    group_off = np.zeros(n_groups + 1, dtype=np.int64)
+    group_off[1:] = np.cumsum(np.bincount(g, minlength=n_groups))
+    sorted_ = bool(np.all(order == np.arange(n_trk)))
+    site_order = spatial_order(site_lon, site_lat, xp)
+    n_site, n_bin = int(site_lon.shape[0]), int(thr.shape[0])
+    idx = xp.as_tensor(order, device=fl.dev) if fl.torch else order
+    rows = (lambda a: a.index_select(0, idx)) if fl.torch else (lambda a: a[order])
+    planes = [fl.contiguous(a if sorted_ else rows(a)) for a in planes]
+    if n_trk == 0:                                          # (never read, but an empty tensor has no pointer to pass)
+        planes = [fl.new((1, n_t), 'f8') for _ in planes]
+    slon, slat = fl.contiguous(site_lon[site_order]), fl.contiguous(site_lat[site_order])
+    extras = [None if a is None else fl.contiguous(a[site_order]) for a in site_extras]
+    counts = fl.new((n_site, n_groups, max(n_bin, 1)), 'i4')
+    smax = fl.new((n_site, max(n_trk, 1)), 'f8') if return_max else None
+    more = [fl.new((max(dict(trk=n_trk, group=n_groups, site=n_site)[axis], 1),), 'f8') for _, axis in more_outputs]
+    ptr = lambda a: None if a is None else fl.ptr(a)                                      # noqa: E731
+    args = make_args(ScanArgs(
+        tracks=dict(n_trk=n_trk, n_t=n_t, row_stride=n_t, n_group=n_groups, group_off=group_off.ctypes.data_as(C.POINTER(C.c_int64))),
+        planes=[ptr(a) for a in planes], sites=(n_site, ptr(slon), ptr(slat)),
+        out=(n_bin, thr.ctypes.data_as(_lib.DP), ptr(counts), ptr(smax)), extras=[ptr(a) for a in extras],
+        outputs=[ptr(a) for a in more]))
+    with fl.context(engine, device) as ctx:
+        ctx.call(entry, *args)
+
+    # back to the caller's site and storm order
+    def by_site(a):
+        out = xp.empty_like(a)
+        out[site_order] = a
+        return out
+    res = dict(counts=by_site(counts), thresholds=thr)
+    for (name, axis), a in zip(more_outputs, more):
+        if axis == 'group':
+            res[name] = a[:n_groups]
+        elif axis == 'site':
+            res[name] = by_site(a)
+        else:
+            res[name] = xp.empty_like(a[:n_trk])
+            res[name][idx] = a[:n_trk]
+    if return_max:
+        out = by_site(smax[:, :n_trk])
+        if not sorted_:
+            un = xp.empty_like(out)
+            un[:, idx] = out
+            out = un
+        res['site_max'] = out
+    return res

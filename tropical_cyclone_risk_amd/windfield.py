@@ -21,8 +21,9 @@ import sys
 
 import numpy as np
 
-from . import _lib, hazard
-from .hazard import _is_tensor
+from . import _lib, analysis, hazard
+from .analysis import DEFAULT_THRESHOLDS, ENV_VARS  # noqa: F401
+from .sitescan import site_scan
 
 MAX_SUBSTEPS = 64
 MAX_R_OUT_KM = 2000.0
@@ -46,7 +47,7 @@ def _track_length(planes, xp):
 
 
 def site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt_s, rmax_km=None, ck_cd=None, r_out_km=500., substeps=1,
-              thresholds=hazard.DEFAULT_THRESHOLDS, return_max=False, engine=None, device=0, n_groups=None):
+              thresholds=DEFAULT_THRESHOLDS, return_max=False, engine=None, device=0, n_groups=None):
     """Peak footprint wind and exceedance counts of every site.
 
     lon, lat, v: [n_trk][n_t] fp64 (the track file's lon_trks, lat_trks, v_trks); env: (u250, v250, u850, v850), each [n_trk][n_t]
@@ -59,29 +60,26 @@ def site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt_s, rmax_km=None, 
     ``thresholds``, and with ``return_max`` ``site_max`` [n_site][n_trk] (m/s; NaN: no sample within r_out_km), in the type and
     on the device of ``lon``.
     """
-    planes, conv, thr, prm = _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
+    planes, fl, thr, prm = _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
 
-    def make_args(tracks, sites, out):
-        return (C.byref(_tracks_struct(tracks)), C.byref(prm)) + sites + out
-    return hazard._site_scan('tcr_windfield', planes, conv, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device,
-                             make_args)
+    def make_args(a):
+        return (C.byref(_tracks_struct(a)), C.byref(prm)) + a.sites + a.out
+    return site_scan('tcr_windfield', planes, fl, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device, make_args)
 
 
-def _tracks_struct(tracks):
-    """tcr_wind_tracks of _site_scan's tracks dict (seven planes, or eight with rmax_km)."""
-    p = tracks.pop('planes') + [None]                      # (no rmax_km plane)
-    return _lib.WindTracks(lon=p[0], lat=p[1], v=p[2], u250=p[3], v250=p[4], u850=p[5], v850=p[6], rmax_km=p[7], **tracks)
+def _tracks_struct(a):
+    """tcr_wind_tracks of site_scan's ScanArgs (seven planes, or eight with rmax_km)."""
+    p = a.planes + [None]                                  # (no rmax_km plane)
+    return _lib.WindTracks(lon=p[0], lat=p[1], v=p[2], u250=p[3], v250=p[4], u850=p[5], v850=p[6], rmax_km=p[7], **a.tracks)
 
 
 def _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups):
-    """The footprint's argument checks (ValueError, before the library is touched): (planes, conv, thresholds, tcr_wind_params),
-    shared with loss.portfolio_loss."""
+    """The footprint's argument checks (ValueError, before the library is touched): (planes, their analysis.Flavour, thresholds,
+    tcr_wind_params), shared with loss.portfolio_loss."""
     if len(env) != 4:
         raise ValueError('env must be (u250, v250, u850, v850)')
-    planes, conv = hazard._as_planes((lon, lat, v) + tuple(env), 'lon, lat, v and the four env planes')
-    xp = np
-    if _is_tensor(planes[0]):
-        import torch as xp
+    planes, fl = analysis.as_planes((lon, lat, v) + tuple(env), 'lon, lat, v and the four env planes')
+    xp = fl.xp
     n_trk, n_t = int(planes[0].shape[0]), int(planes[0].shape[1])
     if n_t < 1:
         raise ValueError('the tracks need at least one sample')
@@ -102,12 +100,12 @@ def _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresho
         raise ValueError('thresholds must be 1 to 64 finite, strictly ascending values')
     rm_const = 0.0
     if rmax_km is not None:
-        if np.ndim(rmax_km.cpu() if _is_tensor(rmax_km) else rmax_km) == 0:
+        if np.ndim(analysis.to_numpy(rmax_km)) == 0:
             rm_const = float(rmax_km)
             if not (np.isfinite(rm_const) and rm_const > 0):
                 raise ValueError('rmax_km must be finite and > 0')
         else:
-            rm_plane = conv(rmax_km)
+            rm_plane = fl.conv(rmax_km)
             if tuple(rm_plane.shape) != (n_trk, n_t):
                 raise ValueError('an rmax_km plane must be [n_trk][n_t]')
             n = _track_length(planes, xp)
@@ -119,29 +117,17 @@ def _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresho
             planes.append(rm_plane)
     if n_groups is not None and int(n_groups) < 1:
         raise ValueError('n_groups must be >= 1')
-    return planes, conv, thr, _lib.WindParams(dt_s=dt_s, ck_cd=ck_cd, r_out_km=r_out_km, rmax_const_km=rm_const, substeps=substeps)
+    return planes, fl, thr, _lib.WindParams(dt_s=dt_s, ck_cd=ck_cd, r_out_km=r_out_km, rmax_const_km=rm_const, substeps=substeps)
 
 
 # ---------------------------------------------------------------------------------------------------------------- CLI
-ENV_VARS = ('u250_trks', 'v250_trks', 'u850_trks', 'v850_trks')
-
-
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog='python -m tropical_cyclone_risk_amd.windfield',
                                 description='Wind-footprint exceedance counts and return periods of track files at sites.')
-    p.add_argument('tracks', nargs='+', help='track files (ensemble members); every year of every file is one group')
-    p.add_argument('--site', type=hazard._site, action='append', default=[], metavar='LON,LAT',
-                   help='repeatable; write --site=LON,LAT when LON is negative')
-    p.add_argument('--sites', metavar='FILE.csv', help='one LON,LAT per line (lines that are not two numbers are skipped)')
-    p.add_argument('--grid', type=hazard._grid, metavar='LON0:LON1:DLON,LAT0:LAT1:DLAT')
-    p.add_argument('--rmax-km', type=float, default=None, help='constant radius of maximum wind (default: Willoughby et al. 2006)')
-    p.add_argument('--r-out-km', type=float, default=500.0)
-    p.add_argument('--substeps', type=int, default=1, help='evaluation points per sample interval (1 = the samples only)')
-    p.add_argument('--ck-cd', type=float, default=None, help='Ck / Cd of the profile (default: the namelist\'s)')
-    p.add_argument('--thresholds', type=lambda t: hazard._range(t, '--thresholds'), default=hazard.DEFAULT_THRESHOLDS,
-                   metavar='LO:HI:STEP')
-    p.add_argument('--out', default='wind.npz')
-    p.add_argument('--device', type=int, default=0)
+    analysis.add_site_args(p)
+    analysis.add_footprint_args(p)
+    analysis.add_threshold_arg(p)
+    analysis.add_track_args(p, 'wind.npz')
     a = p.parse_args(argv)
     if not (a.site or a.sites or a.grid):
         p.error('give sites with --site, --sites or --grid')
@@ -149,29 +135,23 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    from .climatology import sample_spacing
     args = parse_args(argv)
-    site_lon, site_lat = hazard.collect_sites(args)
+    site_lon, site_lat = analysis.collect_sites(args)
     if site_lon.size == 0:
         raise SystemExit('no sites')
-    lon, lat, vmax, groups, gfile, gyear, more = hazard.load_groups(args.tracks, extra=('v_trks',) + ENV_VARS + ('time',))
+    lon, lat, _, v, env, groups, gfile, gyear, dt = analysis.load_wind_planes(args.tracks)
     total_years = len(gfile)
-    dt = sample_spacing(more['time'])
-    v, *env = (np.concatenate([np.asarray(a, dtype=np.float64) for a in more[k]]) for k in ('v_trks',) + ENV_VARS)
     res = site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt, rmax_km=args.rmax_km, ck_cd=args.ck_cd,
                     r_out_km=args.r_out_km, substeps=args.substeps, thresholds=args.thresholds, device=args.device,
                     n_groups=total_years)
     rp = hazard.return_periods(res['counts'], total_years)
     np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,
              total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps,
-             rmax_km=np.nan if args.rmax_km is None else args.rmax_km, dt_s=dt, group_file=gfile, group_year=gyear,
-             files=np.array([str(f) for f in args.tracks]))
+             rmax_km=np.nan if args.rmax_km is None else args.rmax_km, dt_s=dt,
+             **analysis.group_meta(args.tracks, gfile, gyear))
     print('%d sites, %d storms, %d groups (%d files), total_years = %d, r_out = %g km, %d substeps -> %s'
           % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.r_out_km, args.substeps, args.out))
-    if site_lon.size <= 10:
-        print('return period (years) by threshold (m/s): ' + ' '.join('%6g' % t for t in res['thresholds']))
-        for i in range(site_lon.size):
-            print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%6.3g' % x for x in rp[i]))
+    analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp)
     return 0
 
 
