@@ -220,7 +220,9 @@ typedef struct {
     int32_t park_final;       /* a pass of at most this many waves runs to the end (default 8) */
     int32_t table_segments;   /* 0: the forcing table in one piece instead of a second segment written only for the storms the
                                  first integration pass parks (default 1) */
-    int32_t prune;            /* 0: tc_rows_only without the in-flight 2-day test (default 1) */
+    int32_t prune;            /* tc_rows_only: 0 = accept test 1 by a kernel of its own over every storm (k_screen, from the v
+                                 part of the step records); otherwise (default 1) decided in flight by the integrator, which
+                                 lists the storms that pass — when 2 d is an output sample, else as 0 */
     int32_t emit_grid_cap;    /* workgroup rows walking the list of storms that pass accept test 1 (default 8192) */
     int32_t copy_threads;     /* host threads that copy a month slot's planes into the pinned staging buffer (default 4) */
     int32_t reserved;

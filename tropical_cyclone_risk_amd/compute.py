@@ -222,7 +222,8 @@ class GpuRound:
         return True
 
     def can_grow(self):
-        """This rank's HBM holds a doubled step record (per_rank x max_rk_steps x ~400 B in at most half of what is free).
+        """This rank's HBM holds a doubled step record (per_rank x max_rk_steps x ~290 B — ~390 B where k_screen's v records
+        are written as well, which the 400 below covers — in at most half of what is free).
         A local fact: accept_loop combines it over the ranks before anyone grows."""
         cur = int(self.eng.params.max_rk_steps) or 64
         free = self.torch.cuda.mem_get_info(self.pipe.dev)[0] if self.pipe.dev.type == 'cuda' else 1 << 62

@@ -174,7 +174,7 @@ struct tcr_ctx {
     // workspaces
     double *d_fs = nullptr, *d_srec = nullptr;    // forcing tables, accepted-step records
     size_t fs_cap = 0, srec_cap = 0;
-    double *d_vrec = nullptr;                     // the v part of the step records, packed (k_integrate -> k_screen)
+    double *d_vrec = nullptr;                     // the v part of the step records, packed (k_integrate -> k_screen; only when k_screen runs)
     size_t vrec_cap = 0;
     unsigned long long *d_tiles = nullptr;      // scratch of k_compact: ticket, generation, one word per tile (zeroed when allocated)
     size_t tiles_cap = 0;
@@ -190,14 +190,9 @@ struct tcr_ctx {
     size_t pf_cap = 0;
     int fs_period = 0;                          // 0: direct Fourier kernel
     int cu_count = 256;
-    uint8_t *d_screen_skip = nullptr; // storms the integrator found to fail the 2-day test (TC rows only)
-    size_t screen_skip_cap = 0;
-    int32_t *d_und_list = nullptr;    // ... and the storms accept test 1 is still open for (k_screen's work list)
-    size_t und_list_cap = 0;
-    unsigned long long *d_und_count = nullptr;
     float *d_stat32 = nullptr;                  // fp32 copy of the land / bathymetry planes
     bool stat32_stale = true;
-    int32_t *d_tc_idx = nullptr;                // storms that passed accept test 1 (k_screen -> compaction), tc_rows_only
+    int32_t *d_tc_idx = nullptr;                // storms that passed accept test 1 (k_integrate or k_screen -> k_dense / k_emit), tc_rows_only
     size_t tc_idx_cap = 0;
     int64_t *d_tc_count = nullptr;
     double *d_cell = nullptr; size_t cell_cap = 0; int cell_bins = 0;     // scratch of tcr_cell_order_dev
@@ -878,7 +873,6 @@ int integrate_impl(tcr_ctx *ctx, const tcr_storms *in, const TracksT<R> out, voi
     if (grow(ctx, &ctx->d_fs, &ctx->fs_cap, ((size_t)n * ns * 4 * sizeof(R) + 7) / 8)) return -1;
     const int max_rk = P.max_rk_steps > 0 ? P.max_rk_steps : 64;
     if (grow(ctx, &ctx->d_srec, &ctx->srec_cap, (size_t)n * max_rk * REC)) return -1;
-    if (grow(ctx, &ctx->d_vrec, &ctx->vrec_cap, (size_t)n * max_rk * kVRec)) return -1;
     if (max_rk > 65535) return fail(ctx, "tcr_params.max_rk_steps must be <= 65535");
     {
         double *p = reinterpret_cast<double *>(ctx->d_sidx);        // [n][n_steps] uint16: step of each sample
@@ -907,26 +901,28 @@ int integrate_impl(tcr_ctx *ctx, const tcr_storms *in, const TracksT<R> out, voi
     const unsigned final_waves = park_final_waves(ctx);
     const bool segmented = kFsMfmaColGroups == 2 && thr > 0 && waves > final_waves && kMaxPasses > 1 && fourier_on_matrix_cores(ctx) &&
                            (int)P.n_steps > kFsSegSamples + 16 && ctx->tune.table_segments != 0;
-    // TC rows only: the 2-day half of accept test 1 is decided in flight when 2 d is an output sample (KArgsT::prune_sample)
+    // TC rows only: accept test 1 is decided in flight when 2 d is an output sample (KArgsT::prune_sample) — the integrator
+    // appends the storms that pass to the TC list itself; otherwise k_screen decides it from the v part of the step records
     int prune_sample = -1;
     if (out.tc_rows_only && ctx->tune.prune != 0) {
         const double t2d = 2 * 86400.0, step_out = P.total_time / (double)(P.n_steps - 1);
         const int j = (int)floor(t2d / step_out);
-        if (j >= 1 && j < P.n_steps - 1 && ts_host(P, j) == t2d) {
-            prune_sample = j;
-            double *q = reinterpret_cast<double *>(ctx->d_screen_skip);
-            if (grow(ctx, &q, &ctx->screen_skip_cap, ((size_t)n + 7) / 8)) { ctx->d_screen_skip = nullptr; return -1; }
-            ctx->d_screen_skip = reinterpret_cast<uint8_t *>(q);
-            double *u = reinterpret_cast<double *>(ctx->d_und_list);
-            if (grow(ctx, &u, &ctx->und_list_cap, ((size_t)n + 1) / 2 + 1)) { ctx->d_und_list = nullptr; return -1; }
-            ctx->d_und_list = reinterpret_cast<int32_t *>(u);
-            if (!ctx->d_und_count && dev_alloc(ctx, &ctx->d_und_count, (size_t)1)) return -1;
-        }
+        if (j >= 1 && j < P.n_steps - 1 && ts_host(P, j) == t2d) prune_sample = j;
+    }
+    const bool in_flight = prune_sample >= 0;
+    // (a context that has used k_screen keeps its vrec when it changes to the in-flight path: freeing it here would need the
+    // synchronisation and the re-capture of replayed rounds that an allocation needs)
+    if (!in_flight && grow(ctx, &ctx->d_vrec, &ctx->vrec_cap, (size_t)n * max_rk * kVRec)) return -1;
+    if (out.tc_rows_only && (size_t)n > ctx->tc_idx_cap) {
+        if (ctx->d_tc_idx) HIPCHK(ctx, hipFree(ctx->d_tc_idx));
+        ctx->d_tc_idx = nullptr; ctx->tc_idx_cap = 0;
+        if (dev_alloc(ctx, &ctx->d_tc_idx, (size_t)n)) return -1;
+        ctx->tc_idx_cap = (size_t)n;
     }
     {
         BatchReset z{};
         z.queue = ctx->d_queue; z.queue_words = (int)kQueueWords;
-        if (prune_sample >= 0) { z.und_count = ctx->d_und_count; z.flags = out.flags; z.n_flags = n; }
+        if (in_flight) { z.flags = out.flags; z.n_flags = n; }
         if (out.tc_rows_only) z.tc_count = reinterpret_cast<unsigned long long *>(ctx->d_tc_count);
         if (launch_fourier<R>(ctx, n, in->n_dev, in->phases, fs, st, segmented ? kFsFirst : kFsAll, nullptr, nullptr, &z)) return -1;
     }
@@ -936,17 +932,16 @@ int integrate_impl(tcr_ctx *ctx, const tcr_storms *in, const TracksT<R> out, voi
         KArgsT<R> a{};
         a.P = P; a.D = dev_fields(ctx); a.K = EK; a.n = n; a.n_dev = in->n_dev;
         a.lon0 = in->lon0; a.lat0 = in->lat0; a.v0 = in->v0; a.m0 = in->m0; a.h_bl = in->h_bl;
-        a.slot = in->slot; a.phases = in->phases; a.fs = fs; a.srec = ctx->d_srec; a.vrec = ctx->d_vrec; a.max_rk_steps = max_rk;
+        a.slot = in->slot; a.phases = in->phases; a.fs = fs; a.srec = ctx->d_srec; a.vrec = in_flight ? nullptr : ctx->d_vrec; a.max_rk_steps = max_rk;
         a.n_valid = out.n_valid; a.status = out.status; a.nfev = out.nfev;
         a.n_accept = out.n_accept; a.n_reject = out.n_reject;
         a.queue = ctx->d_queue;
         a.prune_sample = prune_sample;
-        a.screen_skip = prune_sample >= 0 ? ctx->d_screen_skip : nullptr;
-        if (prune_sample >= 0) {
-            // storms still open for accept test 1 when they end: the list k_screen works through (flags of the others stay 0)
-            a.und_list = ctx->d_und_list; a.und_count = ctx->d_und_count;
+        if (in_flight) {
+            // storms that pass accept test 1 go on the TC list as they end (flags of the others stay 0)
+            a.tc_list = ctx->d_tc_idx; a.tc_count = reinterpret_cast<unsigned long long *>(ctx->d_tc_count);
         }
-        // (the work queue / pass counters and, with the in-flight 2-day test, flags[] and the open-storm count were zeroed by
+        // (the work queue / pass counters, the TC count and, with accept test 1 in flight, flags[] were zeroed by
         // the batch's first kernel — BatchReset; three hipMemsetAsync until round 4, which as captured memset nodes of a
         // replayed round did not reliably clear flags[]: tests/test_round.py)
         // (a segmented first pass can park any number of its storms)
@@ -984,26 +979,21 @@ int integrate_impl(tcr_ctx *ctx, const tcr_storms *in, const TracksT<R> out, voi
     if (ev) HIPCHK(ctx, hipEventRecord(ev[2], st));
     {
         EArgsT<R> a{};
-        a.P = P; a.D = dev_fields(ctx); a.n = n; a.n_dev = in->n_dev; a.max_rk_steps = max_rk; a.srec = ctx->d_srec; a.vrec = ctx->d_vrec; a.fs = fs;
+        a.P = P; a.D = dev_fields(ctx); a.n = n; a.n_dev = in->n_dev; a.max_rk_steps = max_rk; a.srec = ctx->d_srec; a.vrec = in_flight ? nullptr : ctx->d_vrec; a.fs = fs;
         a.slot = in->slot; a.n_valid = out.n_valid; a.status = out.status; a.n_accept = out.n_accept;
         a.lon = out.lon; a.lat = out.lat; a.v = out.v; a.m = out.m; a.vmax = out.vmax;
         a.envw = out.envw; a.flags = out.flags; a.pad_state = out.pad_state;
         a.K = EK;
-        a.screen_skip = prune_sample >= 0 ? ctx->d_screen_skip : nullptr;
-        if (prune_sample >= 0) { a.und_list = ctx->d_und_list; a.und_count = ctx->d_und_count; }
         const unsigned chunks = (unsigned)((ns + kPostThreads - 1) / kPostThreads);
         if (out.tc_rows_only) {
             // Only what the reference does (compute.py:185-204): accept test 1 from the v series alone, then env
             // winds, vmax and rows for the storms that passed.  The list stays on the device; the grids are
             // sized for the whole batch and workgroups beyond *count leave at once.
-            if ((size_t)n > ctx->tc_idx_cap) {
-                if (ctx->d_tc_idx) HIPCHK(ctx, hipFree(ctx->d_tc_idx));
-                ctx->d_tc_idx = nullptr; ctx->tc_idx_cap = 0;
-                if (dev_alloc(ctx, &ctx->d_tc_idx, (size_t)n)) return -1;
-                ctx->tc_idx_cap = (size_t)n;
+            if (!in_flight) {
+                a.tc_list = ctx->d_tc_idx; a.tc_count = reinterpret_cast<unsigned long long *>(ctx->d_tc_count);
+                hipLaunchKernelGGL(k_screen<R>, dim3((unsigned)((n + kScreenStorms - 1) / kScreenStorms)), dim3(kScreenThreads), 0, st, a);
             }
-            a.tc_list = ctx->d_tc_idx; a.tc_count = reinterpret_cast<unsigned long long *>(ctx->d_tc_count);
-            hipLaunchKernelGGL(k_screen<R>, dim3((unsigned)((n + kScreenStorms - 1) / kScreenStorms)), dim3(kScreenThreads), 0, st, a);
+            // (in flight: the integrator has left the list already; the two stages stay in the trace, empty)
             STAGE(TCR_STAGE_SCREEN);
             STAGE(TCR_STAGE_SELECT_TC);          // (the list is k_screen's own since round 4: no compaction launch)
             a.list = ctx->d_tc_idx; a.count = ctx->d_tc_count;
@@ -1111,7 +1101,7 @@ int tcr_ctx_destroy(tcr_ctx *ctx)
     (void)hipFree(ctx->lf_xy); (void)hipFree(ctx->lf_bits);
     (void)hipFree(ctx->d_cl);
     for (int i = 0; i < 2; ++i) { if (ctx->h_stage[i]) (void)hipHostFree(ctx->h_stage[i]); if (ctx->h_stage_ev[i]) (void)hipEventDestroy(ctx->h_stage_ev[i]); }
-    (void)hipFree(ctx->d_hist_partial); (void)hipFree(ctx->d_cell); (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_tc_idx); (void)hipFree(ctx->d_tc_count); (void)hipFree(ctx->d_queue); (void)hipFree(ctx->d_sidx); (void)hipFree(ctx->d_park[0]); (void)hipFree(ctx->d_park[1]); (void)hipFree(ctx->d_sc_table); (void)hipFree(ctx->d_pf); (void)hipFree(ctx->d_screen_skip); (void)hipFree(ctx->d_und_list); (void)hipFree(ctx->d_und_count); (void)hipFree(ctx->d_tab);
+    (void)hipFree(ctx->d_hist_partial); (void)hipFree(ctx->d_cell); (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_tc_idx); (void)hipFree(ctx->d_tc_count); (void)hipFree(ctx->d_queue); (void)hipFree(ctx->d_sidx); (void)hipFree(ctx->d_park[0]); (void)hipFree(ctx->d_park[1]); (void)hipFree(ctx->d_sc_table); (void)hipFree(ctx->d_pf); (void)hipFree(ctx->d_tab);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return 0;

@@ -40,7 +40,7 @@
 //                         everything a discrete decision of the reference is taken on, or that two kernels must reproduce
 //                         bit for bit: the cell search and bilinear weights (locate_t), every FITPACK bilinear sum (`land == 1`,
 //                         coupled_fast.py:35-38; `PI != 0`, `t_strat == 0`, `-h_m <= bathymetry`), the output grid (ts_k, fs_bracket),
-//                         dense output (dense_at and the integrator's in-flight 2-day sample, which k_screen must reproduce),
+//                         dense output (dense_at, and dense_v_* below: accept test 1 as k_integrate decides it in flight and as k_screen does),
 //                         seeding, wind statistics, thermodynamics;
 //   same value, fewer instructions (on by default)
 //                         TCR_FAST_DIV / TCR_FAST_SQRT: division and square root of fun(t, y) without the range-scaling instructions
@@ -447,6 +447,86 @@ template <typename R>
 __device__ __forceinline__ double ts_k(const EvalKT<R> &K, int i)
 {
     return (i == RD(K.n_steps) - 1) ? RD(K.total_time) : (double)i * RD(K.tstep);
+}
+
+// Dense-output polynomial of RK45 exactly as SciPy spells it (rk.py:409-420)
+__device__ constexpr double RK_P[7][4] = {
+    {1, -8048581381. / 2820520608, 8663915743. / 2820520608, -12715105075. / 11282082432},
+    {0, 0, 0, 0},
+    {0, 131558114200. / 32700410799, -68118460800. / 10900136933, 87487479700. / 32700410799},
+    {0, -1754552775. / 470086768, 14199869525. / 1410260304, -10690763975. / 1880347072},
+    {0, 127303824393. / 49829197408, -318862633887. / 49829197408, 701980252875. / 199316789632},
+    {0, -282668133. / 205662961, 2019193451. / 616988883, -1453857185. / 822651844},
+    {0, 40617522. / 29380423, -110615467. / 29380423, 69997945. / 29380423}};
+
+// The v component of one accepted step's dense output: what accept test 1 (`any(v >= 15) and v(2 d) >= 6.5`, util/compute.py:185-189)
+// is decided on.  One source for the two places that decide it — k_integrate on the step it has just accepted, k_screen on the
+// step's stored record — so that both see the v k_emit writes, bit for bit.  Nothing here is fused or reordered.
+template <typename R>
+struct StepVT {
+    double t_old, h64;       // the step's start and length, fp64 like every time
+    R hh, y0, Q[4];          // (R)h, v at t_old, the v row of Q = K^T P
+    int i_lo, i_hi;          // the output samples [i_lo, i_hi) the step emits (ivp.py:706-723)
+};
+
+// the v row of Q = K^T P (rk.py:179-181) from the step's seven stage derivatives of v: k_dense's sum, operation for operation
+template <typename R>
+__device__ __forceinline__ void dense_v_row(const R (&kq)[7], R (&Q)[4])
+{
+    TCR_FP_EXACT
+    for (int k = 0; k < 4; ++k) {
+        R acc = R(0.0);
+        for (int q = 0; q < 7; ++q) acc += kq[q] * R(RK_P[q][k]);
+        Q[k] = acc;
+    }
+}
+
+// v at output sample i, exactly as dense_at forms it: x = (t_i - t_old) / h, four separately rounded terms, hh * acc + y0
+template <typename R>
+__device__ __forceinline__ R dense_v_at(const tcr_params &P, const StepVT<R> &s, int i)
+{
+    TCR_FP_EXACT
+    const R x = (R)((ts_at(P, i) - s.t_old) / s.h64);
+    const R p1 = x, p2 = p1 * x, p3 = p2 * x, p4 = p3 * x;
+    R acc = R(0.0);
+    acc += s.Q[0] * p1; acc += s.Q[1] * p2; acc += s.Q[2] * p3; acc += s.Q[3] * p4;
+    return s.hh * acc + s.y0;
+}
+
+// `any(v >= v_thresh)` over the samples a step emits.
+// dense_v_below: the step cannot reach the threshold anywhere, so its samples need no look.  On x in [0, 1] every term
+// Q_k x^(k+1) is at most max(Q_k, 0), so v <= y0 + |h| sum max(Q_k, 0) (h > 0 here); the margin (1e-3 m/s; fp32: 1e-2) is
+// orders of magnitude above the rounding of either side.  NaNs are not below: they fall through to the walk.
+template <typename R>
+__device__ __forceinline__ bool dense_v_below(const StepVT<R> &s, R thr)
+{
+    TCR_FP_EXACT
+    const R margin = sizeof(R) == 8 ? R(1e-3) : R(1e-2);
+    const R z = R(0.0);
+    const R up = (s.Q[0] > z ? s.Q[0] : z) + (s.Q[1] > z ? s.Q[1] : z) + (s.Q[2] > z ? s.Q[2] : z) + (s.Q[3] > z ? s.Q[3] : z);
+    const R ub = s.y0 + fabs(s.hh) * up;
+    return ub < thr - margin;
+}
+
+// dense_v_hit: one sample of the walk over a step's samples [i_lo, i_hi), which stops at its first hit.  The sample is first judged
+// with x = (t_i - t_old) * (1 / h) (rh, formed once per step) and Horner's form — within 1e-13 (fp32: 1e-5) of the exact value —
+// and only a sample that lands within `band` of the threshold is evaluated exactly as dense_at does (a wave-uniform branch the
+// compiler cannot turn into straight-line code): the decision is the exact one in every case.
+// (The loop itself stays with the callers: as part of the helper it cost k_screen<double> a register it does not have.)
+template <typename R>
+__device__ __forceinline__ bool dense_v_hit(const tcr_params &P, const StepVT<R> &s, double rh, R thr, int i)
+{
+    TCR_FP_EXACT
+    const R band = sizeof(R) == 8 ? R(1e-9) : R(2e-3);
+    const R x = (R)((ts_at(P, i) - s.t_old) * rh);
+    const R v_f = s.hh * (x * (s.Q[0] + x * (s.Q[1] + x * (s.Q[2] + x * s.Q[3])))) + s.y0;
+    bool hit = v_f >= thr + band;
+    const bool amb = !hit && v_f >= thr - band;
+    if (__ballot(amb)) {
+        asm volatile("" ::: "memory");
+        if (amb) hit = dense_v_at<R>(P, s, i) >= thr;
+    }
+    return hit;
 }
 
 // interp1d(t_s, Fs, axis=1)(t) (scipy/interpolate/_interpolate.py:457-486), split into the

@@ -60,21 +60,29 @@ struct KArgsT {
     uint8_t *probe;
     int probe_cap;
     // what accept test 1 needs of an accepted step, packed: t_old, h, t_new, v_old, K[0..6][v], - (12 doubles, 96 B);
-    // k_screen reads these instead of pulling the whole 288-byte records of every storm through the cache
+    // k_screen reads these instead of pulling the whole 288-byte records of every storm through the cache.
+    // NULL: nobody will read them (accept test 1 is decided in flight, below) and none are written
     double *vrec;                // [n][max_rk_steps][kVRec]
     // TC-rows-only mode: accept test 1 is `any(v >= 15) and v(2 d) >= 6.5`, and when 2 d is an output sample (sample
-    // prune_sample, -1: off) v(2 d) is that sample's v.  The step that emits it evaluates it — with dense_at's arithmetic — and a
-    // storm that fails is marked in screen_skip[storm]: it cannot become a TC, so k_screen skips it and the integrator stops
-    // writing its step records (nothing downstream reads them).
+    // prune_sample; the host sets tc_list exactly then) v(2 d) is that sample's v, or — the track ends before it — the last
+    // sample's.  Every accepted step then judges the v of the samples it emits, from the stage derivatives it still holds in
+    // LDS and with dense_at's arithmetic (tcr_device.h: dense_v_*), so the decision is the one k_screen takes from the
+    // records: a storm that fails the 2-day test stops writing step records (nothing downstream reads them), and a storm
+    // that has passed both halves when it ends is appended to tc_list, the list k_dense / k_emit walk.  k_screen is not launched.
     int prune_sample;
-    uint8_t *screen_skip;        // [n]: written for every storm when it ends (1: failed the 2-day test in flight)
-    int32_t *und_list;           // storms accept test 1 is still open for when they end (neither gated nor failed in flight), any order
-    unsigned long long *und_count;
+    int32_t *tc_list;            // storms that pass accept test 1, any order (NULL: k_screen decides, from vrec)
+    unsigned long long *tc_count;
 };
 using KArgs = KArgsT<double>;
 constexpr int kVRec = 12;
 constexpr int kMaxPasses = 16;
 constexpr int kParkRec = 18;     // doubles per parked storm: t, h, t_new, ha, g, y[4], f[4], 6 x int32, 0.5 Ck / h_bl, field slot
+// k_integrate's per-storm state of accept test 1 (KArgsT::tc_list); it travels in bits 27-30 of the park record's n_reject word
+constexpr int kScrAny15 = 1;     // some sample so far has v >= v_thresh
+constexpr int kScrLastOk = 2;    // 2-day test open (sample prune_sample not emitted yet): the last emitted sample has v >= v_2d_thresh
+constexpr int kScrPassed = 4;    // 2-day test passed
+constexpr int kScrFailed = 8;    // 2-day test failed: not a TC whatever else happens
+constexpr int kScrMask = 15, kScrShift = 27;
 
 // ---------------------------------------------------------------------------
 // gen_f (track/bam_track.py:23-31), direct form: one thread per (storm, sample),
@@ -254,20 +262,18 @@ constexpr int kFsMfmaMaxSamples = 24 * 16;
 // kParkRec); otherwise row r is storm r.
 // What a batch's kernels accumulate into, zeroed by the first kernel of the batch that runs anyway (k_phase_factors_frag;
 // k_batch_reset when the forcing table takes another path): k_integrate's queue heads / parked counts / occupancy counters
-// and — when the 2-day test is decided in flight — flags[0 .. n_flags) and the count of storms accept test 1 is still open for.
+// and — when accept test 1 is decided in flight — flags[0 .. n_flags), which k_dense then marks for the listed storms only.
 struct BatchReset {
     unsigned long long *queue;
     int queue_words;
-    unsigned long long *und_count;
     int32_t *flags;
     int64_t n_flags;
-    unsigned long long *tc_count;       // TC-rows-only: the length of the list k_screen appends to
+    unsigned long long *tc_count;       // TC-rows-only: the length of the list k_integrate / k_screen appends to
 };
 __device__ __forceinline__ void batch_reset(const BatchReset &z, int64_t i, int64_t stride)
 {
     if (!z.queue) return;
     for (int64_t k = i; k < z.queue_words; k += stride) z.queue[k] = 0ull;
-    if (i == 0 && z.und_count) *z.und_count = 0ull;
     if (i == 0 && z.tc_count) *z.tc_count = 0ull;
     for (int64_t k = i; k < z.n_flags; k += stride) z.flags[k] = 0;
 }
@@ -456,14 +462,7 @@ __global__ __launch_bounds__(64 * kFsMfmaWaves, TCR_FS_MFMA_WPS) void k_fourier_
 __device__ constexpr double RK_C[7] = {0, 1. / 5, 3. / 10, 4. / 5, 8. / 9, 1, 1};
 __device__ constexpr double RK_B[6] = {35. / 384, 0, 500. / 1113, 125. / 192, -2187. / 6784, 11. / 84};
 __device__ constexpr double RK_E[7] = {-71. / 57600, 0, 71. / 16695, -71. / 1920, 17253. / 339200, -22. / 525, 1. / 40};
-__device__ constexpr double RK_P[7][4] = {
-    {1, -8048581381. / 2820520608, 8663915743. / 2820520608, -12715105075. / 11282082432},
-    {0, 0, 0, 0},
-    {0, 131558114200. / 32700410799, -68118460800. / 10900136933, 87487479700. / 32700410799},
-    {0, -1754552775. / 470086768, 14199869525. / 1410260304, -10690763975. / 1880347072},
-    {0, 127303824393. / 49829197408, -318862633887. / 49829197408, 701980252875. / 199316789632},
-    {0, -282668133. / 205662961, 2019193451. / 616988883, -1453857185. / 822651844},
-    {0, 40617522. / 29380423, -110615467. / 29380423, 69997945. / 29380423}};
+// (RK_P, the dense-output polynomial, sits in tcr_device.h with the helpers of accept test 1)
 
 __device__ __forceinline__ double rms4(double a, double b, double c, double d)
 {
@@ -519,8 +518,8 @@ template <typename R> constexpr int int_wps() { return sizeof(R) == 8 ? TCR_INT_
 template <typename R, bool AFFINE, bool PROBE, int SM>
 __global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a)
 {
-    // TCR_FUSE_RK (tcr_device.h): stage inputs, y_new, the error norm and the initial-step norms below contract to fmas; the
-    // in-flight 2-day sample does not (k_screen must reproduce it bit for bit), nor does anything inlined from another function
+    // TCR_FUSE_RK (tcr_device.h): stage inputs, y_new, the error norm and the initial-step norms below contract to fmas; nothing
+    // inlined from another function does — in particular not the helpers of accept test 1 (dense_v_*), which k_screen shares
     TCR_FP_FUSE_RK
     // Kl[(stage*4 + component)*64 + lane]
     __shared__ R Kl[7 * 4 * kWave];
@@ -554,7 +553,7 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a
     double *srec = nullptr;
     R ck_h = R(0.0);                        // 0.5 Ck / h_bl of the lane's storm (ck_over_h; travels in the park record)
     int cur_slot = 0;                       // the storm's field slot (travels in the park record)
-    bool doomed = false;                    // failed the 2-day test already (prune_sample): no more records
+    int scr = 0;                            // accept test 1 in flight (tc_list): kScr* bits; kScrFailed: no more records
     R y[4] = {0, 0, 0, 0}, f[4] = {0, 0, 0, 0}, yn[4] = {0, 0, 0, 0};
     R e[4] = {0, 0, 0, 0};                  // evaluation point: lon, lat, v, m
     double et = 0;                          // ... and its time
@@ -571,9 +570,10 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a
         a.nfev[sid] = (status == TCR_STATUS_GATED) ? 0 : nfev;
         a.n_accept[sid] = nacc;
         a.n_reject[sid] = nrej;
-        if (a.screen_skip) a.screen_skip[sid] = doomed ? 1 : 0;
-        if (a.und_list && !doomed && status != TCR_STATUS_GATED && next_out > 0)
-            a.und_list[atomicAdd(a.und_count, 1ull)] = (int32_t)sid;            // k_screen works through this list only
+        // accept test 1, decided in flight: a track that ended before the 2-day sample is judged on its last sample (np.interp clamps)
+        if (a.tc_list && status != TCR_STATUS_GATED && next_out > 0 && (scr & kScrAny15) &&
+            ((scr & kScrPassed) || (!(scr & kScrFailed) && (scr & kScrLastOk))))
+            a.tc_list[atomicAdd(a.tc_count, 1ull)] = (int32_t)sid;              // flags[] stays 0 for the others (BatchReset)
         active = false;
     };
     // one attempt of _step_impl's while-loop: clip to t_bound, stage-2 input (rk.py:137-146, 62-66)
@@ -611,7 +611,7 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a
             const size_t item = (size_t)(base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull)));
             double2 *o = reinterpret_cast<double2 *>(a.park_out + item * kParkRec);
             const long long c0 = (long long)(unsigned)nfev | ((long long)nacc << 32);
-            const long long c1 = (long long)(unsigned)nrej | ((long long)(doomed ? 1 : 0) << 30) | ((long long)(rejected ? 1 : 0) << 31) | ((long long)next_out << 32);
+            const long long c1 = (long long)(unsigned)nrej | ((long long)scr << kScrShift) | ((long long)(rejected ? 1 : 0) << 31) | ((long long)next_out << 32);
             o[0] = make_double2(t, h); o[1] = make_double2(t_new, ha); o[2] = make_double2((double)g, (double)y[0]);
             o[3] = make_double2((double)y[1], (double)y[2]); o[4] = make_double2((double)y[3], (double)f[0]);
             o[5] = make_double2((double)f[1], (double)f[2]);
@@ -652,7 +652,7 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a
                         const double lo0 = a.lon0[sid], la0 = a.lat0[sid], vv0 = a.v0[sid], mm0 = a.m0[sid], hb0 = a.h_bl[sid];
                         slot_id = a.slot[sid];
                         y[0] = (R)lo0; y[1] = (R)la0; y[2] = (R)vv0; y[3] = (R)mm0; ck_h = ck_over_h<R>(K, (R)hb0);
-                        status = kRunning; nfev = 0; nacc = 0; nrej = 0; next_out = 0; doomed = false;
+                        status = kRunning; nfev = 0; nacc = 0; nrej = 0; next_out = 0; scr = 0;
                         t = 0.0;
                         et = 0.0; e[0] = y[0]; e[1] = y[1]; e[2] = y[2]; e[3] = y[3];
                         fresh = true;
@@ -666,7 +666,7 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a
                         sid = __double_as_longlong(r6.y);
                         const long long c0 = __double_as_longlong(r7.x), c1 = __double_as_longlong(r7.y);
                         nfev = (int)(c0 & 0xffffffffll); nacc = (int)(c0 >> 32);
-                        nrej = (int)(c1 & 0x3fffffffll); doomed = (c1 >> 30) & 1; rejected = (c1 >> 31) & 1; next_out = (int)(c1 >> 32);
+                        nrej = (int)(c1 & ((1ll << kScrShift) - 1)); scr = (int)(c1 >> kScrShift) & kScrMask; rejected = (c1 >> 31) & 1; next_out = (int)(c1 >> 32);
                         ck_h = (R)r8.x; slot_id = (int)__double_as_longlong(r8.y);
                         status = kRunning;
                         // stage-2 input exactly as attempt_setup left it
@@ -768,7 +768,8 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a
                         if (rejected && fac > 1) fac = 1;
                         ha *= fac;
                         // step record for k_emit: doubles t_old, h, t_new, -; then R y_old[4], K[7][4]
-                        if (nacc < a.max_rk_steps && !doomed) {
+                        const bool recorded = nacc < a.max_rk_steps && !(scr & kScrFailed);
+                        if (recorded) {
                             double *rec = srec + (size_t)nacc * REC;
                             double2 *o = reinterpret_cast<double2 *>(rec);
                             o[0] = make_double2(t, h);
@@ -780,13 +781,15 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a
                                 V4 kk; kk[0] = KS(j, 0); kk[1] = KS(j, 1); kk[2] = KS(j, 2); kk[3] = KS(j, 3);
                                 body[1 + j] = kk;
                             }
-                            double2 *vr = reinterpret_cast<double2 *>(a.vrec + (sid * (long long)a.max_rk_steps + nacc) * kVRec);
-                            vr[0] = make_double2(t, h);
-                            vr[1] = make_double2(t_new, (double)y[2]);
-                            vr[2] = make_double2((double)KS(0, 2), (double)KS(1, 2));
-                            vr[3] = make_double2((double)KS(2, 2), (double)KS(3, 2));
-                            vr[4] = make_double2((double)KS(4, 2), (double)KS(5, 2));
-                            vr[5] = make_double2((double)KS(6, 2), 0.0);
+                            if (a.vrec) {
+                                double2 *vr = reinterpret_cast<double2 *>(a.vrec + (sid * (long long)a.max_rk_steps + nacc) * kVRec);
+                                vr[0] = make_double2(t, h);
+                                vr[1] = make_double2(t_new, (double)y[2]);
+                                vr[2] = make_double2((double)KS(0, 2), (double)KS(1, 2));
+                                vr[3] = make_double2((double)KS(2, 2), (double)KS(3, 2));
+                                vr[4] = make_double2((double)KS(4, 2), (double)KS(5, 2));
+                                vr[5] = make_double2((double)KS(6, 2), 0.0);
+                            }
                         }
                         ++nacc;
                         const double t_old = t;
@@ -804,32 +807,34 @@ __global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a
                         g = g_new;
                         const int first_out = next_out;
                         next_out = samples_upto(P, t_emit);         // t_eval emission count (ivp.py:706-723)
-                        // the sample np.interp(2 d, res.t, v) reads: the 2-day sample itself, or — the track ends before
-                        // it — the last one emitted (np.interp clamps), if this final step is the one that emits it
-                        int s2d = -1;
-                        if (a.prune_sample >= 0 && !doomed) {
-                            if (first_out <= a.prune_sample && a.prune_sample < next_out) s2d = a.prune_sample;
-                            else if (status != kRunning && next_out <= a.prune_sample && first_out < next_out) s2d = next_out - 1;
-                        }
-                        if (s2d >= 0) {
-                            TCR_FP_EXACT
-                            // its v exactly as dense_at / k_screen form it (row 2 of Q = K^T P, x = (t_i - t_old) / h), and
-                            // accept test 1's second half on it
-                            R Qv[4];
-                            for (int k = 0; k < 4; ++k) {
-                                R acc = R(0.0);
-                                for (int q = 0; q < 7; ++q) acc += KS(q, 2) * R(RK_P[q][k]);
-                                Qv[k] = acc;
+                        // Accept test 1 on the samples [first_out, next_out) this step emits, as k_screen takes it from the step's
+                        // record: steps that leave no record are not looked at, and a storm that has failed is never looked at again.
+                        const bool emits = first_out < next_out;
+                        const bool need2d = emits && !(scr & kScrPassed) && first_out <= a.prune_sample;
+                        const bool need15 = emits && !(scr & kScrAny15);
+                        if (a.tc_list && recorded && (need2d || need15)) {
+                            StepVT<R> sv;
+                            sv.t_old = t_old; sv.h64 = h; sv.hh = (R)h; sv.y0 = v_old; sv.i_lo = first_out; sv.i_hi = next_out;
+                            const R kq[7] = {KS(0, 2), KS(1, 2), KS(2, 2), KS(3, 2), KS(4, 2), KS(5, 2), KS(6, 2)};
+                            dense_v_row<R>(kq, sv.Q);
+                            if (need2d) {
+                                // the sample np.interp(2 d, res.t, v) reads: the 2-day sample itself if this step emits it; until
+                                // then the last one emitted, which is the one that counts if the track ends before 2 d
+                                const bool at2d = a.prune_sample < next_out;
+                                const bool ok = (double)dense_v_at<R>(P, sv, at2d ? a.prune_sample : next_out - 1) >= P.v_2d_thresh;
+                                if (at2d) scr |= ok ? kScrPassed : kScrFailed;
+                                else scr = ok ? (scr | kScrLastOk) : (scr & ~kScrLastOk);
                             }
-                            const R x = (R)((ts_at(P, s2d) - t_old) / h);
-                            const R p1 = x, p2 = p1 * x, p3 = p2 * x, p4 = p3 * x;
-                            R acc = R(0.0);
-                            acc += Qv[0] * p1; acc += Qv[1] * p2; acc += Qv[2] * p3; acc += Qv[3] * p4;
-                            const R v2d = (R)h * acc + v_old;
-                            doomed = !((double)v2d >= P.v_2d_thresh);
+                            const bool reach = need15 && !(scr & kScrFailed) && !dense_v_below<R>(sv, (R)P.v_thresh);
+                            if (__ballot(reach)) {
+                                const double rh = 1.0 / h;
+                                bool hit = !reach;          // (a lane that cannot reach the threshold walks nothing)
+                                for (int i = sv.i_lo; i < sv.i_hi && !hit; ++i) hit = dense_v_hit<R>(P, sv, rh, (R)P.v_thresh, i);
+                                if (reach && hit) scr |= kScrAny15;
+                            }
                         }
-                        // (a doomed storm writes no records and nobody reads any: it cannot overflow its record — ADVICE r2)
-                        if (status == kRunning && !doomed && nacc >= a.max_rk_steps) status = TCR_STATUS_STEP_OVERFLOW;
+                        // (a failed storm writes no records and nobody reads any: it cannot overflow its record — ADVICE r2)
+                        if (status == kRunning && !(scr & kScrFailed) && nacc >= a.max_rk_steps) status = TCR_STATUS_STEP_OVERFLOW;
                         if (status != kRunning) finalize();
                         else begin_step();
                     } else {
@@ -922,9 +927,6 @@ struct EArgsT {
     const int32_t *list;
     const int64_t *count;
     int64_t item_base;           // k_emit's overflow launch: first list entry it handles
-    const uint8_t *screen_skip;  // k_screen: storms the integrator already found to fail the 2-day test (KArgsT::screen_skip; NULL: none)
-    const int32_t *und_list;     // k_screen: if set, only these storms are looked at (KArgsT::und_list); flags[] was zeroed beforehand
-    const unsigned long long *und_count;
     int32_t *tc_list;            // k_screen (TC rows only): appends the storms that pass accept test 1 ...
     unsigned long long *tc_count;    // ... counted here (zeroed by the batch reset)
     EvalKT<R> K;                 // built on the host; k_emit's small workgroups copy it to LDS
@@ -1193,18 +1195,14 @@ __global__ __launch_bounds__(kScreenThreads, TCR_SHADOW_WPS) void k_screen(EArgs
     __shared__ R cap[kScreenStorms][3];      // v at sample j2d, j2d + 1, n - 1
     const tcr_params &P = a.P;
     const int g = threadIdx.x / kScreenGroup, l = threadIdx.x % kScreenGroup;
-    const int64_t item = (int64_t)blockIdx.x * kScreenStorms + g;
-    if (a.und_list && (int64_t)blockIdx.x * kScreenStorms >= (int64_t)*a.und_count) return;      // uniform per workgroup
-    const bool listed = a.und_list && item < (int64_t)*a.und_count;
-    const int64_t sid = a.und_list ? (listed ? (int64_t)a.und_list[item] : 0) : item;
-    const bool on = a.und_list ? listed : sid < a.n;                       // writes a flag
-    const bool exists = a.und_list ? listed : sid < n_eff(a.n, a.n_dev);   // has a storm behind it
+    const int64_t sid = (int64_t)blockIdx.x * kScreenStorms + g;
+    const bool on = sid < a.n;                       // writes a flag
+    const bool exists = sid < n_eff(a.n, a.n_dev);   // has a storm behind it
     const int ns = P.n_steps;
     int n = 0, nst = 0, st = TCR_STATUS_GATED;
     if (exists) {
         n = a.n_valid[sid]; nst = a.n_accept[sid]; st = a.status[sid];
         nst = nst < a.max_rk_steps ? nst : a.max_rk_steps;
-        if (a.screen_skip && a.screen_skip[sid]) n = 0;        // not a TC whatever else happened; its records stop at day 2
     }
     // np.interp(2 d, res.t, v): which samples it reads (compute.py:186-188; same as k_flags)
     const double step_out = P.total_time / (double)(ns - 1);
@@ -1214,11 +1212,7 @@ __global__ __launch_bounds__(kScreenThreads, TCR_SHADOW_WPS) void k_screen(EArgs
     bool any15 = false;
     const double *vrec_storm = a.vrec + sid * (int64_t)a.max_rk_steps * kVRec;
     // One accepted step of the storm: the v row of Q = K^T P and the samples the step emits
-    struct StepV {
-        double t_old, h64;
-        R hh, y0, Q[4];
-        int i_lo, i_hi;
-    };
+    typedef StepVT<R> StepV;
     auto load_step = [&](int j) {
         // (values were stored widened to fp64; narrowing back gives the R values k_dense reads from the full record)
         const double2 *rj = reinterpret_cast<const double2 *>(vrec_storm + (size_t)j * kVRec);
@@ -1228,24 +1222,14 @@ __global__ __launch_bounds__(kScreenThreads, TCR_SHADOW_WPS) void k_screen(EArgs
         const double t_new = r1.x;
         s.hh = (R)s.h64; s.y0 = (R)r1.y;
         const R kq[7] = {(R)r2.x, (R)r2.y, (R)r3.x, (R)r3.y, (R)r4.x, (R)r4.y, (R)r5.x};
-        for (int k = 0; k < 4; ++k) {
-            R acc = R(0.0);
-            for (int q = 0; q < 7; ++q) acc += kq[q] * R(RK_P[q][k]);
-            s.Q[k] = acc;
-        }
+        dense_v_row<R>(kq, s.Q);
         s.i_lo = (j == 0) ? 0 : samples_upto(P, s.t_old);
         s.i_hi = samples_upto(P, t_new);
         s.i_hi = s.i_hi < n ? s.i_hi : n;
         return s;
     };
-    // dense output of v at sample i, exactly as dense_at forms it: x = (t_i - t_old) / h
-    auto v_at = [&](const StepV &s, int i) -> R {
-        const R x = (R)((ts_at(P, i) - s.t_old) / s.h64);
-        const R p1 = x, p2 = p1 * x, p3 = p2 * x, p4 = p3 * x;
-        R acc = R(0.0);
-        acc += s.Q[0] * p1; acc += s.Q[1] * p2; acc += s.Q[2] * p3; acc += s.Q[3] * p4;
-        return s.hh * acc + s.y0;
-    };
+    // dense output of v at sample i, exactly as dense_at forms it
+    auto v_at = [&](const StepV &s, int i) -> R { return dense_v_at<R>(P, s, i); };
     // ---- phase 1: the 2-day test (three exact samples at most) — most storms fail it, and those need no more
     auto caps = [&](const StepV &s) {
         if (s.i_lo <= j2d && j2d < s.i_hi) cap[g][0] = v_at(s, j2d);
@@ -1265,31 +1249,13 @@ __global__ __launch_bounds__(kScreenThreads, TCR_SHADOW_WPS) void k_screen(EArgs
         pass2d = v2d >= P.v_2d_thresh;
     }
     // ---- phase 2: `any(v >= v_thresh)` over the hourly samples, only for the storms that passed.
-    // A step whose dense output cannot reach the threshold anywhere is skipped without looking at its samples:
-    // on x in [0, 1] every term Q_k x^(k+1) is at most max(Q_k, 0), so v <= y0 + |h| sum max(Q_k, 0) (h > 0 here); the
-    // margin (1e-3 m/s; fp32: 1e-2) is orders of magnitude above the rounding of either side.  A step that can
-    // reach it is walked until its first hit.  Each sample is first judged with x = (t_i - t_old) * (1 / h) and
-    // Horner's form — within 1e-13 (fp32: 1e-5) of the exact value — and only a sample that lands within `band` of the
-    // threshold is evaluated exactly as dense_at does (a wave-uniform branch the compiler cannot turn into
-    // straight-line code): the decision is the exact one in every case.
-    const R thr = (R)P.v_thresh, band = sizeof(R) == 8 ? R(1e-9) : R(2e-3), margin = sizeof(R) == 8 ? R(1e-3) : R(1e-2);
+    // A step whose dense output cannot reach the threshold anywhere is skipped without looking at its samples; a step that
+    // can reach it is walked until its first hit (dense_v_below, dense_v_hit: tcr_device.h).
+    const R thr = (R)P.v_thresh;
     auto scan = [&](const StepV &s) {
-        const R z = R(0.0);
-        const R up = (s.Q[0] > z ? s.Q[0] : z) + (s.Q[1] > z ? s.Q[1] : z) + (s.Q[2] > z ? s.Q[2] : z) + (s.Q[3] > z ? s.Q[3] : z);
-        const R ub = s.y0 + fabs(s.hh) * up;
-        if (ub < thr - margin) return;                  // NaNs fall through to the walk
+        if (dense_v_below<R>(s, thr)) return;
         const double rh = 1.0 / s.h64;
-        for (int i = s.i_lo; i < s.i_hi && !any15; ++i) {
-            const R x = (R)((ts_at(P, i) - s.t_old) * rh);
-            const R v_f = s.hh * (x * (s.Q[0] + x * (s.Q[1] + x * (s.Q[2] + x * s.Q[3])))) + s.y0;
-            bool hit = v_f >= thr + band;
-            const bool amb = !hit && v_f >= thr - band;
-            if (__ballot(amb)) {
-                asm volatile("" ::: "memory");
-                if (amb) hit = v_at(s, i) >= thr;
-            }
-            any15 = any15 || hit;
-        }
+        for (int i = s.i_lo; i < s.i_hi && !any15; ++i) any15 = any15 || dense_v_hit<R>(P, s, rh, thr, i);
     };
     if (pass2d) {
         if (has0) scan(s0);
