@@ -689,6 +689,56 @@ int tcr_loss_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_wind_pa
                   const double *site_lon, const double *site_lat, const double *site_value, const double *site_v_half, int32_t n_bin,
                   const double *thresholds, int32_t *counts, double *event_loss, double *year_agg, double *year_max, double *site_loss);
 
+/* ---- rainfall footprint: storm-total rain and peak rain rate at sites from a radial rain-rate profile ---------------- */
+/* replaces: nothing in the reference's code; the freshwater half of the risk, on the three planes every track file has.  The rate
+ * is R-CLIPER (Tuleya, DeMaria & Kuligowski 2007): a function of the distance from the centre and of vmax alone.  R = 6378.1 km
+ * (util/constants.py earth_R), as in the wind footprint.
+ *   track           a storm's leading run of n samples where lon, lat and vmax are all finite (later samples are ignored; the
+ *                   wind footprint's rule, not the hazard's compaction: time weights need contiguous samples).  A track of
+ *                   fewer than 2 samples has no records.
+ *   records         substeps = m >= 1: the track samples, and between samples k and k + 1 sub-samples at tau = j / m,
+ *                   j = 1 .. m - 1, with lat and vmax linear in tau (y_k + tau (y_k+1 - y_k)), lon the same with its difference
+ *                   reduced to [-180, 180) (the short way round): n_rec = (n - 1) m + 1 records, in time order.  Record q
+ *                   carries the trapezoid weight w_q = dt_s / (3600 m) hours, halved for q = 0 and q = n_rec - 1.
+ *   rate (mm/h)     of a record at distance r (km):
+ *                     V_kt = clamp(vmax 3600 / 1852, v_lo_kt, v_hi_kt),  U = 1 + (V_kt - 35) / 33
+ *                     T0 = a[0] + b[0] U,  Tm = a[1] + b[1] U   (inches / day);   rm = a[2] + b[2] U,  re = a[3] + b[3] U   (km)
+ *                     rate_in_day = T0 + (Tm - T0) r / rm  for r < rm,   Tm exp(-(r - rm) / re)  for r >= rm
+ *                     rate = max(rate_in_day, 0) 25.4 / 24
+ *                   Defaults (the callers': the library has none) are the TRMM fit, a = (-1.10, -1.60, 64.5, 150.0),
+ *                   b = (3.96, 4.80, -13.0, -16.0), and the clamp v_lo_kt = 35, v_hi_kt = 155: a depression rains like a
+ *                   minimal tropical storm, and with these coefficients rm(U) reaches zero at 165.7 kt (U = 64.5 / 13).
+ *   per (site, q)   r = haversine distance with R; the record is included iff r <= r_out_km.
+ *   site_value      [n_site][n_trk] (optional, NULL: not written), NaN when no record of the storm is included at the site;
+ *                   stat = TCR_RAIN_TOTAL: the sum of w_q rate_q(r) over the included records, added in record order (mm);
+ *                   stat = TCR_RAIN_PEAK_RATE: the max of rate_q(r) over the included records (mm/h).
+ *   counts          [n_site][n_group][n_bin] (int32): storms s in [group_off[g], group_off[g + 1]) with site_value >= thresholds[b].
+ * Arguments: dt_s finite and > 0, 0 < r_out_km <= 2000, 1 <= substeps <= 64, stat 0 or 1, 0 < v_lo_kt <= v_hi_kt finite, all
+ * eight coefficients finite, and rm > 0, re > 0, Tm >= 0 at both clamp ends (all are linear in U, so also in between; T0 may be
+ * negative: the rate is clamped at 0); n_trk >= 0, 1 <= n_t <= 2^20, row_stride >= n_t, 1 <= n_bin <= 64, thresholds finite and
+ * strictly ascending, group_off non-decreasing from 0 to n_trk.  Every message begins with "tcr_rainfall:".
+ * Not modelled: rain asymmetry from shear or topography, and decay after landfall.
+ * A site's sum of a storm is one accumulator over exactly the included records in record order, whatever else the call holds
+ * (skipped blocks of far storms contain no included record), and the max and the integer counts do not depend on order: results
+ * are bit-identical from run to run, whatever the launch shape, the site order or the storm order.  Sites in a spatially coherent
+ * order (runs of 64 neighbours) run fastest.  _dev: planes, sites, counts and site_value are device memory, asynchronous on
+ * `stream`; group_off and thresholds are host memory in both entry points.  The workspace is the context's fourth (next to the
+ * hazard's, the footprint's and the loss's): calls of tcr_rainfall_* on one context must be ordered, but one may be in flight next
+ * to a tcr_hazard_*, tcr_windfield_* or tcr_loss_* call on another stream. */
+#define TCR_RAIN_TOTAL 0
+#define TCR_RAIN_PEAK_RATE 1
+typedef struct {
+    double dt_s, r_out_km, v_lo_kt, v_hi_kt;
+    double a[4], b[4];                     /* T0, Tm, rm, re = a[i] + b[i] U */
+    int32_t substeps, stat;
+} tcr_rain_params;
+int tcr_rainfall_dev(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const tcr_rain_params *prm, int64_t n_site, const double *site_lon,
+                     const double *site_lat, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_value, void *stream);
+int tcr_rainfall_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const tcr_rain_params *prm, int64_t n_site, const double *site_lon,
+                      const double *site_lat, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_value);
+/* (site, record) pairs the last tcr_rainfall_* call of this context evaluated after culling; waits for that call */
+int tcr_rainfall_pairs(tcr_ctx *ctx, int64_t *pairs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ TCR_ABI_VERSION = 7
 TCR_NW, TCR_NCOV, TCR_MAX_SERIES, TCR_N_BASINS = 4, 10, 32, 7
 STATUS_GATED, STATUS_FINISHED, STATUS_EVENT, STATUS_STEP_FAIL, STATUS_STEP_OVERFLOW = -1, 0, 1, -2, -3
 FLAG_IS_TC, FLAG_ACCEPTED = 1, 2
+RAIN_TOTAL, RAIN_PEAK_RATE = 0, 1        # TCR_RAIN_*: tcr_rain_params.stat
 STAGES = ('start', 'seed', 'select', 'order', 'gather', 'fourier', 'integrate', 'screen', 'select_tc', 'dense', 'emit', 'flags', 'stats', 'pack')
 STATIC_MODES = ('f64', 'f64_split', 'pack16', 'u8_f32', 'pack64')     # StaticMode (tcr_static_info)
 N_STATS = 10        # TCR_N_STATS: words of a tcr_stats_dev / tcr_round.stats counter block
@@ -38,7 +39,7 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_allgather_rows_dev', 'tcr_allgather_counts_dev', 'tcr_allreduce_sum_i64_dev', 'tcr_concat_rows_dev',
            'tcr_hazard_dev', 'tcr_hazard_host', 'tcr_hazard_pairs', 'tcr_land_upload', 'tcr_land_info', 'tcr_landfall_dev',
            'tcr_landfall_host', 'tcr_climatology_dev', 'tcr_climatology_host', 'tcr_windfield_dev', 'tcr_windfield_host',
-           'tcr_windfield_pairs', 'tcr_loss_dev', 'tcr_loss_host')
+           'tcr_windfield_pairs', 'tcr_loss_dev', 'tcr_loss_host', 'tcr_rainfall_dev', 'tcr_rainfall_host', 'tcr_rainfall_pairs')
 TCR_COMM_ID_BYTES = 128
 
 
@@ -139,6 +140,13 @@ class WindParams(C.Structure):
 class LossParams(C.Structure):
     """tcr_loss_params: threshold and (scalar) half-damage wind of the damage function of tcr_loss_*."""
     _fields_ = [('v_thresh', C.c_double), ('v_half', C.c_double)]
+
+
+class RainParams(C.Structure):
+    """tcr_rain_params: sample spacing, outer radius, the clamp on vmax (knots), the R-CLIPER coefficients (T0, Tm, rm, re =
+    a[i] + b[i] U), sub-steps and the statistic (RAIN_TOTAL, RAIN_PEAK_RATE) of tcr_rainfall_*."""
+    _fields_ = [('dt_s', C.c_double), ('r_out_km', C.c_double), ('v_lo_kt', C.c_double), ('v_hi_kt', C.c_double),
+                ('a', C.c_double * 4), ('b', C.c_double * 4), ('substeps', C.c_int32), ('stat', C.c_int32)]
 
 
 class TcrError(RuntimeError):
@@ -278,6 +286,10 @@ def lib():
     L.tcr_loss_dev.argtypes = [C.c_void_p, C.POINTER(WindTracks), C.POINTER(WindParams), C.POINTER(LossParams), C.c_int64] + \
         [C.c_void_p] * 4 + [C.c_int32, DP] + [C.c_void_p] * 6
     L.tcr_loss_host.argtypes = L.tcr_loss_dev.argtypes[:-1]
+    L.tcr_rainfall_dev.argtypes = [C.c_void_p, C.POINTER(HazardTracks), C.POINTER(RainParams), C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.c_int32, DP, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tcr_rainfall_host.argtypes = L.tcr_rainfall_dev.argtypes[:-1]
+    L.tcr_rainfall_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     if L.tcr_abi_version() != TCR_ABI_VERSION:
         raise TcrError('libtcrisk_hip.so ABI version %d != binding version %d'
                        % (L.tcr_abi_version(), TCR_ABI_VERSION))

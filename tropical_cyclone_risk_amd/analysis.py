@@ -1,4 +1,4 @@
-"""What the analyses of track files (hazard, landfall, climatology, windfield, loss) share: NumPy-or-torch planes, the library
+"""What the analyses of track files (hazard, landfall, climatology, windfield, loss, rainfall) share: NumPy-or-torch planes, the library
 context of one call, the group index of the storms, reading (file, year) groups from track files, and the pieces of their
 command lines.  The per-site scan they share on top of this is sitescan.py."""
 import argparse
@@ -264,10 +264,10 @@ def collect_sites(args):
     return np.array(lon, dtype=np.float64), np.array(lat, dtype=np.float64)
 
 
-def print_return_periods(thresholds, site_lon, site_lat, rp):
-    """The return-period table of up to 10 sites (more: nothing)."""
+def print_return_periods(thresholds, site_lon, site_lat, rp, unit='m/s'):
+    """The return-period table of up to 10 sites (more: nothing).  unit: of the thresholds."""
     if site_lon.size > 10:
         return
-    print('return period (years) by threshold (m/s): ' + ' '.join('%6g' % t for t in thresholds))
+    print('return period (years) by threshold (%s): ' % unit + ' '.join('%6g' % t for t in thresholds))
     for i in range(site_lon.size):
         print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%6.3g' % v for v in rp[i]))

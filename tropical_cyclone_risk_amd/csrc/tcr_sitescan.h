@@ -1,4 +1,5 @@
-// The site scan: what the per-site analyses of a track ensemble (tcr_hazard.hip, tcr_windfield.hip) share.  Each of them turns
+// The site scan: what the per-site analyses of a track ensemble (tcr_hazard.hip, tcr_windfield.hip, tcr_loss.hip, tcr_rainfall.hip)
+// share.  Each of them turns
 // every storm into a row of wave-uniform records, and wants
 //
 //   site_max[site][storm] = max of value(site, record) over the storm's records with haversine(site, record) <= R   (NaN: none)
@@ -17,8 +18,12 @@
 //                   the buffers tile_loss [n_tile][n_trk] and site_part [n_chunk][n_site].  Per storm the wave sums its 64 lane
 //                   losses with a fixed butterfly and lane 0 stores the sum; every lane keeps a running sum of its own losses in
 //                   storm order.  Policies without kLoss compile to the code they had before the variant existed.
-// and calls scan_run with a workspace of its own (ScanWs, two instances in tcr_ctx: a hazard call and a footprint call may be in
-// flight on different streams of one context).
+//                   A policy with `static constexpr bool kSum = true` (tcr_rainfall.hip) turns max into a sum at compile time:
+//                   site_max[site][storm] = sum of value(site, record) over the same records, in record order (NaN: none).  The
+//                   first included record replaces the NaN start, every later one is added to it: nothing is ever added to a NaN.
+//                   kSum with kLoss is a static_assert.  Policies without kSum compile to the code they had before it existed.
+// and calls scan_run with a workspace of its own (ScanWs, four instances in tcr_ctx: a hazard, a footprint, a loss and a rainfall
+// call may be in flight on different streams of one context).
 //
 //   k_site_scan      one wave per (tile of 64 sites, chunk of storms of one group): every lane holds one site's terms in registers;
 //                    the records are wave-uniform and come through scalar loads.  A storm or segment whose cap is farther than R
@@ -29,6 +34,14 @@
 // the rounding of the cap arithmetic), so a skipped pair is always farther than R.  It changes which pairs are evaluated, never a
 // result: a pair's value does not depend on the other pairs, max and integer sums do not depend on order, so results are
 // bit-identical whatever the launch shape.
+//
+// The same holds for a kSum policy, although an fp64 sum does depend on its order.  A lane's sum of a storm runs over exactly the
+// storm's records with a <= a_R, in record order: segments ascending, records ascending inside a segment, one lane, one accumulator.
+// A culled storm or segment holds none of those records (culling is conservative), so skipping it removes no term and moves none;
+// padding records have NaN terms, fail a <= a_R and never reach the sum.  Which tile a site is in, which lane it has, which chunk
+// the storm is in and which other storms and sites the call has change which segments are culled, never the terms or their order.
+// So the sum is bit-identical whatever the launch shape, the site order and the storm order.  This rests on site_max being written
+// by the one lane that accumulated it: no cross-lane or cross-chunk reduction may ever touch it.
 
 namespace {
 
@@ -105,6 +118,12 @@ struct scan_has_loss : std::false_type {};
 template <class P>
 struct scan_has_loss<P, std::void_t<decltype(P::kLoss)>> : std::bool_constant<P::kLoss> {};
 
+// Policy::kSum when the policy has one, false otherwise
+template <class P, class = void>
+struct scan_has_sum : std::false_type {};
+template <class P>
+struct scan_has_sum<P, std::void_t<decltype(P::kSum)>> : std::bool_constant<P::kSum> {};
+
 // cap (centre = the record at `mid`, radius = the largest angle from it) of the records [b, e) of one row
 template <class Rec>
 __device__ void hz_cap(const Rec *row, int b, int e, HzCap *out)
@@ -176,6 +195,8 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
     const unsigned long long n_lanes = (unsigned long long)min<int64_t>(64, a.n_site - site0);
     unsigned long long pairs = 0;
     constexpr bool kLoss = scan_has_loss<Policy>::value;
+    constexpr bool kSum = scan_has_sum<Policy>::value;
+    static_assert(!(kSum && kLoss), "the loss variant of the scan is defined on a max");
     [[maybe_unused]] double loss_acc = 0.0;             // kLoss: this site's losses of the chunk's storms, summed in storm order
     [[maybe_unused]] auto terms = [&] { if constexpr (kLoss) return pol.site_terms(my, valid); else return 0; }();
     __syncthreads();
@@ -195,7 +216,11 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
                 for (int j = 0; j < kHzSeg; ++j) {                  // (padding records fail the test: NaN terms)
                     const Rec p = Rec::uniform(seg + j);
                     const double q = hz_a(me.sp, me.cp, me.sl, me.cl, me.cosp, p.sp, p.cp, p.sl, p.cl, p.cosp);
-                    if (q <= a.a_R) m = fmax(m, pol.value(me, p, q));   // fmax skips NaN: the start, or a NaN value
+                    if constexpr (kSum) {
+                        if (q <= a.a_R) { const double v = pol.value(me, p, q); m = isnan(m) ? v : m + v; }   // in record order
+                    } else {
+                        if (q <= a.a_R) m = fmax(m, pol.value(me, p, q));   // fmax skips NaN: the start, or a NaN value
+                    }
                 }
             }
         }
