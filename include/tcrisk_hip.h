@@ -225,7 +225,8 @@ typedef struct {
                                  lists the storms that pass — when 2 d is an output sample, else as 0 */
     int32_t emit_grid_cap;    /* workgroup rows walking the list of storms that pass accept test 1 (default 8192) */
     int32_t copy_threads;     /* host threads that copy a month slot's planes into the pinned staging buffer (default 4) */
-    int32_t reserved;
+    int32_t table_factors;    /* 0: the forcing table's phase factors by a kernel of their own (k_phase_factors_frag, fragments in
+                                 HBM); otherwise (default 1) formed inside the table kernel from the phases */
 } tcr_tune;
 int tcr_tune_set(tcr_ctx *ctx, const tcr_tune *t);
 int tcr_tune_get(tcr_ctx *ctx, tcr_tune *t);

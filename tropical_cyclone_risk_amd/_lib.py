@@ -99,7 +99,7 @@ class Round(C.Structure):
 
 class Tune(C.Structure):
     """tcr_tune: launch-shape knobs (negative = the library's choice)."""
-    _fields_ = [(k, C.c_int32) for k in ('waves', 'park', 'park_final', 'table_segments', 'prune', 'emit_grid_cap', 'copy_threads', 'reserved')]
+    _fields_ = [(k, C.c_int32) for k in ('waves', 'park', 'park_final', 'table_segments', 'prune', 'emit_grid_cap', 'copy_threads', 'table_factors')]
 
 
 class HazardTracks(C.Structure):

@@ -479,7 +479,7 @@ tcr_tune tune_from_env()
     t.prune = (int32_t)env_long("TCR_PRUNE", -1);
     t.emit_grid_cap = (int32_t)env_long("TCR_EMIT_GRID_CAP", -1);
     t.copy_threads = (int32_t)env_long("TCR_COPY_THREADS", -1);
-    t.reserved = 0;
+    t.table_factors = (int32_t)env_long("TCR_TABLE_FACTORS", -1);
     return t;
 }
 
@@ -796,7 +796,8 @@ int launch_fourier(tcr_ctx *ctx, int64_t n, const int64_t *n_dev, const double *
                    FsPart part = kFsAll, const double *park = nullptr, const unsigned long long *park_count = nullptr,
                    const BatchReset *reset = nullptr)
 {
-    // the batch's counters are zeroed by the phase-factor kernel when there is one, else by a launch of their own
+    // the batch's counters are zeroed by the batch's first kernel that runs anyway — the fused table kernel, or the phase-factor
+    // kernel when tcr_tune.table_factors = 0 — else by a launch of their own
     BatchReset z{};
     if (reset) z = *reset;
     if (reset && !(ctx->fs_period > 0 && fourier_on_matrix_cores(ctx)))
@@ -805,30 +806,33 @@ int launch_fourier(tcr_ctx *ctx, int64_t n, const int64_t *n_dev, const double *
     if (ctx->fs_period > 0) {
         const size_t lds = sizeof(double2) * (size_t)ctx->fs_period;
         const int64_t nf = n * 4 * (int64_t)P.n_series;
-        if (part != kFsRest) {          // (kFsRest reads what the first segment's call left in d_pf: no reallocation in between)
+        // table_factors: the table kernel forms its A fragments from the phases itself; d_pf exists only for the paths that read it
+        const bool fused = fourier_on_matrix_cores(ctx) && ctx->tune.table_factors != 0;
+        if (!fused && part != kFsRest) {        // (kFsRest reads what the first segment's call left in d_pf: no reallocation in between)
             double *p = reinterpret_cast<double *>(ctx->d_pf);
             if (grow(ctx, &p, &ctx->pf_cap, (size_t)nf * 2)) { ctx->d_pf = nullptr; return -1; }
             ctx->d_pf = reinterpret_cast<double2 *>(p);
-        } else if (!ctx->d_pf) return fail(ctx, "internal: second table segment without the first");
+        } else if (!fused && !ctx->d_pf) return fail(ctx, "internal: second table segment without the first");
         if (fourier_on_matrix_cores(ctx)) {
             // matrix-core form: phase factors in MFMA fragment order (4 KB per 4 storms <= the 3.84 KB of d_pf's layout + padding)
             const int64_t tiles = (n + 3) / 4;
             // kFsRest: the second segment for the parked storms is ONE launch (round 6; three until then): the table kernel reads the
-            // storm ids straight out of the park records (word 13 of each, k_integrate's park()) and picks every storm's phase
-            // factors out of the fragments the first segment's k_phase_factors_frag wrote for the whole batch — d_pf is not written
-            // between the two segments (only this function writes it, and a batch's two calls are on one stream)
+            // storm ids straight out of the park records (word 13 of each, k_integrate's park()) and forms every storm's phase
+            // factors from its phases — or, table_factors = 0, picks them out of the fragments the first segment's
+            // k_phase_factors_frag wrote for the whole batch: d_pf is not written between the two segments (only this function
+            // writes it, and a batch's two calls are on one stream)
             const int64_t *list = nullptr;
             int list_stride = 1;
             if (part == kFsRest) {
                 list = reinterpret_cast<const int64_t *>(park) + 13;
                 list_stride = kParkRec;
-            } else {
+            } else if (!fused) {
                 double *p0 = reinterpret_cast<double *>(ctx->d_pf);
                 if (grow(ctx, &p0, &ctx->pf_cap, (size_t)tiles * kFsMfmaKSteps * 64)) { ctx->d_pf = nullptr; return -1; }
                 ctx->d_pf = reinterpret_cast<double2 *>(p0);
                 hipLaunchKernelGGL(k_phase_factors_frag, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st, P, n, n_dev, phases, p0, nullptr, nullptr, z);
             }
-            double *p = reinterpret_cast<double *>(ctx->d_pf);
+            const double *p = fused ? phases : reinterpret_cast<const double *>(ctx->d_pf);
             const int groups = part == kFsAll ? kFsMfmaColGroups : 1;
             // workgroups per launch: TCR_FS_WGS=<total> overrides (scheduling experiment: a workgroup's two 191-register waves
             // keep integrator waves of other batches off their SIMDs)
@@ -837,12 +841,20 @@ int launch_fourier(tcr_ctx *ctx, int64_t n, const int64_t *n_dev, const double *
             want = tcr_exp::fs_workgroups(want, groups);
 #endif
             const unsigned wgs = (unsigned)std::min<int64_t>(tiles, std::max<int64_t>(1, want));
-            if (part == kFsRest)
-                hipLaunchKernelGGL((k_fourier_mfma<R, true>), dim3(wgs, groups), dim3(64 * kFsMfmaWaves), 0, st, P, n, n_dev, ctx->fs_period,
-                                   ctx->d_sc_table, p, fs, 1, list, list_stride, park_count);
+            const dim3 grid(wgs, groups), block(64 * kFsMfmaWaves);
+            const BatchReset none{};
+            if (part == kFsRest && fused)
+                hipLaunchKernelGGL((k_fourier_mfma<R, true, true>), grid, block, 0, st, P, n, n_dev, ctx->fs_period,
+                                   ctx->d_sc_table, p, fs, 1, list, list_stride, park_count, none);
+            else if (part == kFsRest)
+                hipLaunchKernelGGL((k_fourier_mfma<R, true, false>), grid, block, 0, st, P, n, n_dev, ctx->fs_period,
+                                   ctx->d_sc_table, p, fs, 1, list, list_stride, park_count, none);
+            else if (fused)
+                hipLaunchKernelGGL((k_fourier_mfma<R, false, true>), grid, block, 0, st, P, n, n_dev, ctx->fs_period,
+                                   ctx->d_sc_table, p, fs, 0, list, list_stride, park_count, z);
             else
-                hipLaunchKernelGGL((k_fourier_mfma<R, false>), dim3(wgs, groups), dim3(64 * kFsMfmaWaves), 0, st, P, n, n_dev, ctx->fs_period,
-                                   ctx->d_sc_table, p, fs, 0, list, list_stride, park_count);
+                hipLaunchKernelGGL((k_fourier_mfma<R, false, false>), grid, block, 0, st, P, n, n_dev, ctx->fs_period,
+                                   ctx->d_sc_table, p, fs, 0, list, list_stride, park_count, none);
         } else {
             hipLaunchKernelGGL(k_phase_factors, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, P, n, n_dev, phases, ctx->d_pf);
             hipLaunchKernelGGL(k_fourier_periodic<R>, dim3((unsigned)n), dim3(kFsThreads), lds, st, P, n, n_dev,

@@ -227,11 +227,11 @@ __global__ __launch_bounds__(kFsThreads) void k_fourier_periodic(tcr_params P, i
 // one-period table laid out per (harmonic, sample) — the same B for every storm.  A workgroup of two waves owns a column
 // group of 12 tiles = 192 samples (wave w: tiles 6w .. 6w+5 of the group; two groups = 384 samples; group0 selects the
 // first group of a launch, so a launch writes the whole table or one of its two segments), keeps its B fragments in
-// registers for its whole life (96 VGPRs) and walks row tiles of 4 storms x 4 series: 8 coalesced loads of the A fragment
-// (written in fragment order by k_phase_factors_frag), 8 x v_mfma_f64_16x16x4_f64 per column tile on six independent
+// registers for its whole life (96 VGPRs) and walks row tiles of 4 storms x 4 series: the A fragment (formed by the workgroup
+// in LDS, or — not FUSED — 8 coalesced loads of what k_phase_factors_frag wrote in fragment order), 8 x v_mfma_f64_16x16x4_f64 per column tile on six independent
 // accumulator chains, and — rows ordered series-major — a lane ends up with the four series of one (storm, sample) in
 // its four accumulator registers: one 32-byte store per lane, 512 contiguous bytes per storm and instruction.
-// No LDS, no index arithmetic in the loop; 43 k FMAs per storm run on the matrix pipe (the fp64 matrix peak of gfx950
+// No index arithmetic in the loop; 43 k FMAs per storm run on the matrix pipe (the fp64 matrix peak of gfx950
 // equals its vector peak, so the gain is the table reads and integer work of k_fourier_periodic, not a higher ceiling).
 // Summation order differs from k_fourier_periodic (k ascending within an MFMA, fused) at the 1e-16 level; the bound
 // against NumPy's own evaluation stays the one stated in tests/test_gpu_parity.py.
@@ -260,8 +260,8 @@ constexpr int kFsMfmaMaxSamples = 24 * 16;
 // k_fourier_mfma<LIST>: row r of the product is storm list[r * list_stride], r < *list_count (the second segment of the table, written
 // only for the storms the first integration pass parked: `list` points at the storm-id word of k_integrate's park records, stride
 // kParkRec); otherwise row r is storm r.
-// What a batch's kernels accumulate into, zeroed by the first kernel of the batch that runs anyway (k_phase_factors_frag;
-// k_batch_reset when the forcing table takes another path): k_integrate's queue heads / parked counts / occupancy counters
+// What a batch's kernels accumulate into, zeroed by the first kernel of the batch that runs anyway (the fused k_fourier_mfma of
+// the first table segment, or k_phase_factors_frag; k_batch_reset when the forcing table takes another path): k_integrate's queue heads / parked counts / occupancy counters
 // and — when accept test 1 is decided in flight — flags[0 .. n_flags), which k_dense then marks for the listed storms only.
 struct BatchReset {
     unsigned long long *queue;
@@ -276,6 +276,12 @@ __device__ __forceinline__ void batch_reset(const BatchReset &z, int64_t i, int6
     for (int64_t k = i; k < z.queue_words; k += stride) z.queue[k] = 0ull;
     if (i == 0 && z.tc_count) *z.tc_count = 0ull;
     for (int64_t k = i; k < z.n_flags; k += stride) z.flags[k] = 0;
+}
+// One weighted phase factor pair: the expression k_phase_factors_frag stores and the fused k_fourier_mfma forms for itself
+// (one definition, so the two paths of tcr_tune.table_factors give the same bits)
+__device__ __forceinline__ void phase_factor(double wgt, double x, double &cb, double &sb)
+{
+    sb = wgt * sinpi(2.0 * x); cb = wgt * cospi(2.0 * x);
 }
 __global__ __launch_bounds__(256) void k_batch_reset(BatchReset z)
 {
@@ -300,8 +306,7 @@ __global__ __launch_bounds__(256) void k_phase_factors_frag(tcr_params P, int64_
         if (h < N && row < ne) {
             const int64_t storm = list ? list[row] : row;
             const double x = phases[storm * 4 * N + s * N + h];                 // phases are [storm][series][harmonic]
-            const double wgt = P.fs_wgt[h];
-            sb = wgt * sinpi(2.0 * x); cb = wgt * cospi(2.0 * x);
+            phase_factor(P.fs_wgt[h], x, cb, sb);
         }
         const int k = 2 * h;                                                    // k & 3 is 0 or 2: k and k + 1 share a k step
         double *o = frag + tile * (kFsMfmaKSteps * 64) + (k >> 2) * 64 + i;
@@ -310,15 +315,27 @@ __global__ __launch_bounds__(256) void k_phase_factors_frag(tcr_params P, int64_
     }
 }
 
-template <typename R, bool LIST>
+// FUSED (tcr_tune.table_factors, the default): `frag` is the batch's phases [storm][4][n_series] and the workgroup forms the A
+// fragment of each row tile itself — its threads compute the tile's 256 (harmonic, row) pairs with k_phase_factors_frag's own
+// per-thread expression into a double-buffered 4 KB of LDS that every wave reads as A[ks]; the factors of the next row tile
+// are computed between the MFMAs of the current one, from phases loaded one row tile earlier still.  LIST: row r is storm
+// list[r * list_stride] and the thread reads that storm's own 480 bytes of phases (no gather out of whole-batch fragments).
+// A FUSED launch that is not LIST is the batch's first kernel and zeroes what BatchReset names.
+template <typename R, bool LIST, bool FUSED>
 __global__ __launch_bounds__(64 * kFsMfmaWaves, TCR_FS_MFMA_WPS) void k_fourier_mfma(tcr_params P, int64_t n, const int64_t *__restrict__ n_dev,
                                                          int period, const double2 *__restrict__ sc_table,
                                                          const double *__restrict__ frag, R *__restrict__ fs, int group0,
                                                          const int64_t *__restrict__ list, int list_stride,
-                                                         const unsigned long long *__restrict__ list_count)
+                                                         const unsigned long long *__restrict__ list_count, BatchReset z)
 {
     typedef double D4 __attribute__((ext_vector_type(4)));
     __shared__ double stage[kFsMfmaWaves][4 * 16 * 4];     // per wave: one output tile, [storm][sample][series]
+    __shared__ double afrag[FUSED ? 2 : 1][FUSED ? kFsMfmaKSteps * 64 : 1];     // FUSED: A fragments of this and the next row tile
+    __shared__ int64_t asid[FUSED && LIST ? 2 : 1][4];                          // ... and, LIST, the storms behind their four rows
+    constexpr int kThreads = 64 * kFsMfmaWaves, kPairs = 256 / kThreads;        // (harmonic, row) pairs per thread of a row tile
+    static_assert(kPairs * kThreads == 256, "a row tile's 256 factor pairs must divide among the workgroup's threads");
+    if (FUSED && !LIST)
+        batch_reset(z, ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kThreads + threadIdx.x, (int64_t)gridDim.x * gridDim.y * kThreads);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int N = P.n_series, ns = P.n_steps;
     const int64_t ne = LIST ? (int64_t)*list_count : n_eff(n, n_dev);      // rows of the product (LIST: row r is storm list[r])
@@ -410,18 +427,80 @@ __global__ __launch_bounds__(64 * kFsMfmaWaves, TCR_FS_MFMA_WPS) void k_fourier_
             for (int ks = 0; ks < kFsMfmaKSteps; ++ks) dst[ks] = (t < tiles) ? frag[t * (kFsMfmaKSteps * 64) + ks * 64 + lane] : 0.0;
         }
     };
+    // FUSED: thread r of the workgroup owns row fi of the tile and harmonics fh + u * (kThreads / 16) — k_phase_factors_frag's
+    // r = threadIdx.x, h = r >> 4, i = r & 15 dealt over fewer threads.  Three row tiles are in flight: the fragment being
+    // multiplied (afrag[cur]), the phases fx of the next tile (factors formed between this tile's MFMAs into afrag[cur ^ 1]) and
+    // — LIST — the storm id fsid behind this thread's row of the tile after that, so that no load is waited for where it is issued.
+    const int fi = threadIdx.x & 15, fh = threadIdx.x >> 4;
+    auto row_storm = [&](int64_t t) -> int64_t {               // storm behind row fi of tile t; -1: no such row
+        const int64_t r = t * 4 + (fi & 3);
+        if (r >= ne) return -1;
+        return LIST ? list[r * (int64_t)list_stride] : r;
+    };
+    double fx[kPairs], fw[kPairs];                              // fw: the weights of this thread's harmonics, read once (a per-lane
+    int64_t fx_sid = -1;                                        // read of P is a memory load, and one in the loop waits for the stores)
+#pragma unroll
+    for (int u = 0; u < kPairs; ++u) { const int h = fh + u * (kThreads / 16); fw[u] = (FUSED && h < N) ? P.fs_wgt[h] : 0.0; }
+    auto load_phases = [&](int64_t storm) {
+        fx_sid = storm;
+        const bool fx_row = storm >= 0;
+#pragma unroll
+        for (int u = 0; u < kPairs; ++u) {
+            const int h = fh + u * (kThreads / 16);
+            fx[u] = (fx_row && h < N) ? frag[storm * 4 * N + (fi >> 2) * N + h] : 0.0;        // phases are [storm][series][harmonic]
+        }
+    };
+    auto form_factors = [&](int u, double *dst, int64_t *sid) { // pair u of this thread from fx into the fragment at dst
+        if (LIST && u == 0 && threadIdx.x < 4) sid[threadIdx.x] = fx_sid;
+        const int h = fh + u * (kThreads / 16);
+        double cb = 0.0, sb = 0.0;
+        if (fx_sid >= 0 && h < N) phase_factor(fw[u], fx[u], cb, sb);
+        const int k = 2 * h;
+        double *o = dst + (k >> 2) * 64 + fi;
+        o[(k & 3) * 16] = cb;
+        o[((k & 3) + 1) * 16] = sb;
+    };
     double A[kFsMfmaKSteps];
     int64_t tile = blockIdx.x;
-    load_frag(tile, A);
+    int64_t fsid = -1;
+    int cur = 0;
+    if (FUSED) {
+        load_phases(row_storm(tile));
+#pragma unroll
+        for (int u = 0; u < kPairs; ++u) form_factors(u, afrag[0], asid[0]);
+        load_phases(row_storm(tile + gridDim.x));
+        fsid = row_storm(tile + 2 * (int64_t)gridDim.x);
+        __syncthreads();
+    } else {
+        load_frag(tile, A);
+    }
+    // (the trip count is the same for every wave of the workgroup: the FUSED loop ends in a workgroup barrier)
     for (; tile < tiles; tile += gridDim.x) {
         // the storms behind this row tile's rows (LIST: loaded here, with the fragment loads, long before the stores need
         // them — a load next to the stores would put a vmcnt(0), i.e. the stores' whole write latency, in front of each)
         const int64_t r0 = tile * 4 + (sizeof(R) == 8 ? (lane >> 5) : q), r1 = r0 + 2;
         int64_t cs0 = r0, cs1 = r1;
-        if (LIST) { cs0 = list[(r0 < ne ? r0 : ne - 1) * (int64_t)list_stride]; cs1 = list[(r1 < ne ? r1 : ne - 1) * (int64_t)list_stride]; }
+        // (FUSED: out of LDS, where the threads that formed the tile's factors left them — no global load that a store would wait for)
+        if (LIST && FUSED) { cs0 = asid[cur][r0 & 3]; cs1 = asid[cur][r1 & 3]; }
+        else if (LIST) { cs0 = list[(r0 < ne ? r0 : ne - 1) * (int64_t)list_stride]; cs1 = list[(r1 < ne ? r1 : ne - 1) * (int64_t)list_stride]; }
         // next row tile's fragment while this one multiplies
         double An[kFsMfmaKSteps];
-        load_frag(tile + gridDim.x, An);
+        if (FUSED) {
+#pragma unroll
+            for (int ks = 0; ks < kFsMfmaKSteps; ++ks) A[ks] = afrag[cur][ks * 64 + lane];
+        } else {
+            load_frag(tile + gridDim.x, An);
+        }
+        // FUSED: the next tile's factors, cut into pieces like the epilogue and issued between the MFMAs of the first column tile
+        bool formed = false;                                    // wave-uniform
+        auto factor_piece = [&](int piece) {
+            if (piece >= 1 && piece <= kPairs) form_factors(piece - 1, afrag[cur ^ 1], asid[LIST ? cur ^ 1 : 0]);
+            if (piece == kPairs + 1) {
+                load_phases(fsid);                                              // of tile + 2 * gridDim.x
+                fsid = row_storm(tile + 3 * (int64_t)gridDim.x);
+                formed = true;
+            }
+        };
 #pragma unroll
         for (int t = 0; t < kFsMfmaColTiles; ++t) {
             const int k0 = (((blockIdx.y + group0) * kFsMfmaWaves + wave) * kFsMfmaColTiles + t) * 16;
@@ -431,12 +510,22 @@ __global__ __launch_bounds__(64 * kFsMfmaWaves, TCR_FS_MFMA_WPS) void k_fourier_
             for (int ks = 0; ks < kFsMfmaKSteps; ++ks) {
                 acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[ks], B[t][ks], acc, 0, 0, 0);
                 epilogue_piece(ks);                              // of the previous tile
+                if (FUSED && t == 0) factor_piece(ks);
                 __builtin_amdgcn_sched_barrier(0);               // keep this interleaving
             }
             ep.v = acc; ep.tile = tile; ep.k0 = k0; ep.s0 = cs0; ep.s1 = cs1; ep.live = true;
         }
+        if (FUSED) {
+            if (!formed) {                                      // a wave without a column tile inside the track still supplies its factors
 #pragma unroll
-        for (int ks = 0; ks < kFsMfmaKSteps; ++ks) A[ks] = An[ks];
+                for (int piece = 0; piece < kFsMfmaKSteps; ++piece) factor_piece(piece);
+            }
+            __syncthreads();                                    // afrag[cur ^ 1] is complete, afrag[cur] has been read
+            cur ^= 1;
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < kFsMfmaKSteps; ++ks) A[ks] = An[ks];
+        }
     }
 #pragma unroll
     for (int piece = 0; piece < 8; ++piece) epilogue_piece(piece);

@@ -344,17 +344,17 @@ class TCEngine:
         return self
 
     def tune(self, **kw):
-        """Launch-shape knobs (tcr_tune: waves, park, park_final, table_segments, prune, emit_grid_cap, copy_threads; a negative
-        value = the library's choice).  Results do not depend on them.  Returns the knobs now in effect."""
+        """Launch-shape knobs (tcr_tune: waves, park, park_final, table_segments, prune, emit_grid_cap, copy_threads,
+        table_factors; a negative value = the library's choice).  Results do not depend on them.  Returns the knobs now in effect."""
         t = _lib.Tune()
         self._ck(self.L.tcr_tune_get(self.h, C.byref(t)))
         for k, v in kw.items():
-            if k not in dict(_lib.Tune._fields_) or k == 'reserved':
+            if k not in dict(_lib.Tune._fields_):
                 raise TypeError('unknown tuning knob %r' % k)
             setattr(t, k, int(v))
         if kw:
             self._ck(self.L.tcr_tune_set(self.h, C.byref(t)))
-        return {k: getattr(t, k) for k, _ in _lib.Tune._fields_ if k != 'reserved'}
+        return {k: getattr(t, k) for k, _ in _lib.Tune._fields_}
 
     def stage_timing(self, reset=True):
         """Host milliseconds of this engine's slot uploads since the last reset (tcr_stage_timing)."""
