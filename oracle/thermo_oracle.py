@@ -6,8 +6,9 @@ sat_deficit (:92-104), get_LCL (:107-126, Romps 2017 through scipy.special.lambe
 calc_T_rho (:129-134) and CAPE_PI_vectorized (:266-412) for select_thermo = 1, select_interp = 2
 (namelist.py:59-60), plus the chi clip and mid-level pick of calc_thermo.compute_thermo (:55-74).
 
-Pinned: tests/test_thermo.py checks it against tests/golden/thermo_cases.npz, which
-tests/golden/make_golden_thermo.py produced by running the reference's own functions.
+Pinned: tests/test_thermo.py checks it against tests/golden/thermo_cases.npz and, at ERA5's own levels and on two to
+four levels, tests/golden/thermo_cases_era5.npz, which tests/golden/make_golden_thermo{,_era5}.py produced by running
+the reference's own functions.
 Only tests/ may import this module.
 """
 import math
@@ -169,16 +170,50 @@ def potential_intensity(table, cecd, sst, p_surf, p_env, T_env, r_env):
     cape = cape if cape != cape else max(cape, 0.0)
     cape = 0.0 if cape != cape else cape
     with np.errstate(all='ignore'):
-        x = cecd * float(np.float64(sst) / np.float64(T_out_s)) * (capes - cape)
+        x_raw = x = cecd * float(np.float64(sst) / np.float64(T_out_s)) * (capes - cape)
         x = x if x != x else max(x, 0.0)
         pi = math.sqrt(x) if x == x else NAN
-    return (0.0 if pi != pi else pi), dict(p_lcl=p_lcl, s_ns=s_ns, ss=ss, i_cond=i_cond, a_out=a_out, s_out=s_out)
+    aux = dict(p_lcl=p_lcl, s_ns=s_ns, ss=ss, i_cond=i_cond, a_out=a_out, s_out=s_out, x=x_raw)
+    aux.update(_decisions(cecd, sst, T_out_s, p_env, p_lcl, i_cond, a_out, s_out, tre, tra, trs, dlnp))
+    # what the rule "the top level is on the moist adiabat whatever the LCL" (:322) changes: the parcel's density temperature
+    # there minus the dry adiabat's, 0 where the LCL puts the level on the moist adiabat anyway
+    with np.errstate(all='ignore'):
+        dry_top = t_rho(float(T_ns * np.power(np.float64(p_env[-1]) / p_ns, Rd / cp)), r_ns)
+    aux['top_rule'] = tra[-1] - dry_top if not p_lcl > p_env[-1] else 0.0
+    aux['dT1_a'] = tra[a_out] - tre[a_out]
+    return (0.0 if pi != pi else pi), aux
+
+
+def _runs(hit):
+    return sum(1 for k in range(len(hit)) if hit[k] and (k == 0 or not hit[k - 1]))
+
+
+def _decisions(cecd, sst, T_out_s, p_env, p_lcl, i_cond, a_out, s_out, tre, tra, trs, dlnp):
+    """What a comparison against this column may rest on; none of it enters PI.
+    scale: the sums behind x with every term taken absolute (a NaN term counts 0, as the reference's nan -> 0 drops it);
+    runs_*: separate runs of levels with the parcel not denser than the environment;
+    margin: the nearest any `tr >= tre` test comes to a tie, relative to tre.  Level 0 of the unsaturated parcel is left
+    out below the LCL: there p / p_ns is 1, tra is tre bit for bit in any arithmetic, and the test is a tie every
+    implementation decides alike;
+    lcl_margin: the nearest `p_lcl > p` comes to a tie, relative to p."""
+    L = len(p_env)
+    with np.errstate(all='ignore'):
+        terms = [Rd * abs(tra[k] - tre[k]) * abs(dlnp[k]) for k in range(a_out + 1)] + \
+                [Rd * abs(trs[k] - tre[k]) * abs(dlnp[k]) for k in range(s_out + 1)]
+        scale = cecd * abs(float(np.float64(sst) / np.float64(T_out_s))) * sum(t for t in terms if t == t)
+        m = [abs(trs[k] - tre[k]) / abs(tre[k]) for k in range(L)]
+        m += [abs(tra[k] - tre[k]) / abs(tre[k]) for k in range(1 if i_cond > 0 else 0, L)]
+        m = [v for v in m if v == v]
+        lm = [abs(p_lcl - p) / p for p in p_env] if p_lcl == p_lcl else []
+    return dict(scale=scale, runs_a=_runs([tra[k] >= tre[k] for k in range(L)]), runs_s=_runs([trs[k] >= tre[k] for k in range(L)]),
+                margin=min(m) if m else math.inf, lcl_margin=min(lm) if lm else math.inf)
 
 
 def sat_deficit(sst, ps, T, pm, rv):
+    """(:92-104); also the three entropies it is made of."""
     sp, sps, spss = s_unsat(T, pm, rv), s_sat(T, pm), s_sat(sst, ps)
     with np.errstate(all='ignore'):
-        return float(np.float64(sps - sp) / np.float64(spss - sps))
+        return float(np.float64(sps - sp) / np.float64(spss - sps)), dict(sp=sp, sps=sps, spss=spss)
 
 
 def conv_q_to_rh(T, q, p):
@@ -195,6 +230,6 @@ def column_fields(table, cecd, p_env, sst, psl, T, r, k_mid):
     for idx in np.ndindex(shape):
         col = (slice(None),) + idx
         pi[idx] = potential_intensity(table, cecd, float(sst[idx]), float(psl[idx]), p_env, T[col], r[col])[0]
-        chi[idx] = sat_deficit(float(sst[idx]), float(psl[idx]), float(T[(k_mid,) + idx]), float(p_env[k_mid]), float(r[(k_mid,) + idx]))
+        chi[idx] = sat_deficit(float(sst[idx]), float(psl[idx]), float(T[(k_mid,) + idx]), float(p_env[k_mid]), float(r[(k_mid,) + idx]))[0]
         rh[idx] = conv_q_to_rh(float(T[(k_mid,) + idx]), float(r[(k_mid,) + idx]), float(p_env[k_mid]))
     return pi, chi, rh
