@@ -740,6 +740,43 @@ int tcr_rainfall_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const tcr_r
 /* (site, record) pairs the last tcr_rainfall_* call of this context evaluated after culling; waits for that call */
 int tcr_rainfall_pairs(tcr_ctx *ctx, int64_t *pairs);
 
+/* ---- compound hazard: joint exceedance of footprint wind and storm rain at sites ------------------------------------- */
+/* replaces: nothing in the reference's code; the compound event behind flood-plus-wind exposure, outage models and parametric
+ * covers: how many storms bring a site a wind of at least u AND a rain of at least p.  The count needs both values of every
+ * (site, storm) pair at once, so both footprints are evaluated in one scan and the joint histogram is built there; the
+ * [n_site][n_trk] planes are optional outputs.
+ *   track           a storm's leading run of samples where all eight planes are finite: the seven of tcr_wind_tracks and vmax
+ *                   [n_trk][row_stride] (the rainfall's third plane).  Records and sub-steps as in both sections above.
+ *   W, site_wind    what tcr_windfield_* writes to site_max on that track with `wind`;  P, site_rain: what tcr_rainfall_* writes
+ *                   to site_value on (lon, lat, vmax) cut to that track with `rain` (stat TCR_RAIN_TOTAL or TCR_RAIN_PEAK_RATE).
+ *                   Both [n_site][n_trk], optional (NULL: not written).  A record counts for each hazard under that hazard's own
+ *                   r_out_km, so W can be NaN where P is not.  On storms whose eight planes are finite over the track the seven
+ *                   (or three) give, W and P are bit for bit the two entry points' outputs.
+ *   kw, kr          the number of wind_thresholds <= W and of rain_thresholds <= P; 0 for a NaN.
+ *   counts          [n_site][n_group][n_wbin + 1][n_rbin + 1] (int32): storms of the group with kw >= a and kr >= b.  Index 0 on
+ *                   an axis is "no condition on this hazard": counts[..][1:][0] are the wind footprint's counts, counts[..][0][1:]
+ *                   the rainfall's, counts[..][1:][1:] the joint (AND) table and counts[..][0][0] the size of the group.  The OR
+ *                   table follows by inclusion-exclusion: wind + rain - and.
+ * Arguments: those of tcr_windfield_* and of tcr_rainfall_* under the same rules, each list of thresholds under the rule of its own
+ * entry point, and wind->dt_s == rain->dt_s, wind->substeps == rain->substeps, (n_wbin + 1) (n_rbin + 1) <= 64.  Every message
+ * begins with "tcr_compound:".  rm > 0 and finite at every sample of a track: tcr_compound_host checks the rmax_km plane as
+ * tcr_windfield_host does; tcr_compound_dev cannot, and drops a storm with a bad rm (NaN on both planes at every site, counted
+ * only at index 0 of both axes).  Results are a max of per-pair values, a sum of one accumulator in record order and integer
+ * counts: bit-identical from run to run, whatever the launch shape, the site order or the storm order.  _dev: planes, vmax,
+ * sites, counts, site_wind and site_rain are device memory, asynchronous on `stream`; group_off and both threshold lists are host
+ * memory in both entry points.  The workspace is the context's fifth: calls of tcr_compound_* on one context must be ordered, but
+ * one may be in flight next to a tcr_hazard_*, tcr_windfield_*, tcr_loss_* or tcr_rainfall_* call on another stream. */
+int tcr_compound_dev(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const double *vmax, const tcr_wind_params *wind,
+                     const tcr_rain_params *rain, int64_t n_site, const double *site_lon, const double *site_lat, int32_t n_wbin,
+                     const double *wind_thresholds, int32_t n_rbin, const double *rain_thresholds, int32_t *counts, double *site_wind,
+                     double *site_rain, void *stream);
+int tcr_compound_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const double *vmax, const tcr_wind_params *wind,
+                      const tcr_rain_params *rain, int64_t n_site, const double *site_lon, const double *site_lat, int32_t n_wbin,
+                      const double *wind_thresholds, int32_t n_rbin, const double *rain_thresholds, int32_t *counts, double *site_wind,
+                      double *site_rain);
+/* (site, record) pairs the last tcr_compound_* call of this context evaluated after culling with the larger radius; waits for it */
+int tcr_compound_pairs(tcr_ctx *ctx, int64_t *pairs);
+
 #ifdef __cplusplus
 }
 #endif

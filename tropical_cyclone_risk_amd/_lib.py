@@ -39,7 +39,8 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_allgather_rows_dev', 'tcr_allgather_counts_dev', 'tcr_allreduce_sum_i64_dev', 'tcr_concat_rows_dev',
            'tcr_hazard_dev', 'tcr_hazard_host', 'tcr_hazard_pairs', 'tcr_land_upload', 'tcr_land_info', 'tcr_landfall_dev',
            'tcr_landfall_host', 'tcr_climatology_dev', 'tcr_climatology_host', 'tcr_windfield_dev', 'tcr_windfield_host',
-           'tcr_windfield_pairs', 'tcr_loss_dev', 'tcr_loss_host', 'tcr_rainfall_dev', 'tcr_rainfall_host', 'tcr_rainfall_pairs')
+           'tcr_windfield_pairs', 'tcr_loss_dev', 'tcr_loss_host', 'tcr_rainfall_dev', 'tcr_rainfall_host', 'tcr_rainfall_pairs',
+           'tcr_compound_dev', 'tcr_compound_host', 'tcr_compound_pairs')
 TCR_COMM_ID_BYTES = 128
 
 
@@ -290,6 +291,10 @@ def lib():
                                    C.c_int32, DP, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tcr_rainfall_host.argtypes = L.tcr_rainfall_dev.argtypes[:-1]
     L.tcr_rainfall_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.tcr_compound_dev.argtypes = [C.c_void_p, C.POINTER(WindTracks), C.c_void_p, C.POINTER(WindParams), C.POINTER(RainParams), C.c_int64,
+                                   C.c_void_p, C.c_void_p, C.c_int32, DP, C.c_int32, DP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tcr_compound_host.argtypes = L.tcr_compound_dev.argtypes[:-1]
+    L.tcr_compound_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     if L.tcr_abi_version() != TCR_ABI_VERSION:
         raise TcrError('libtcrisk_hip.so ABI version %d != binding version %d'
                        % (L.tcr_abi_version(), TCR_ABI_VERSION))

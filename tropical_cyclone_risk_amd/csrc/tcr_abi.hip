@@ -229,9 +229,10 @@ struct tcr_ctx {
     std::vector<hipEvent_t> st_pool;
     std::vector<int> st_id;
     size_t st_used = 0;
-    // site hazard (tcr_hazard.hip), wind footprint (tcr_windfield.hip), portfolio loss (tcr_loss.hip) and rainfall
-    // (tcr_rainfall.hip): a workspace each, so that one call of each may be in flight on streams of their own
-    ScanWs hz, wf, ls, rf;
+    // site hazard (tcr_hazard.hip), wind footprint (tcr_windfield.hip), portfolio loss (tcr_loss.hip), rainfall
+    // (tcr_rainfall.hip) and compound hazard (tcr_compound.hip): a workspace each, so that one call of each may be in flight on
+    // streams of their own
+    ScanWs hz, wf, ls, rf, cp;
     // landfall (tcr_landfall.hip): node coordinates (lon, then lat) and land bit plane of the uploaded grid
     double *lf_xy = nullptr;
     uint32_t *lf_bits = nullptr;
@@ -1109,7 +1110,7 @@ int tcr_ctx_destroy(tcr_ctx *ctx)
     for (auto &ev : ctx->st_pool) if (ev) (void)hipEventDestroy(ev);
     for (auto &g : ctx->graphs) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); }
     (void)hipFree(ctx->d_round_key);
-    ctx->hz.release(); ctx->wf.release(); ctx->ls.release(); ctx->rf.release();
+    ctx->hz.release(); ctx->wf.release(); ctx->ls.release(); ctx->rf.release(); ctx->cp.release();
     (void)hipFree(ctx->lf_xy); (void)hipFree(ctx->lf_bits);
     (void)hipFree(ctx->d_cl);
     for (int i = 0; i < 2; ++i) { if (ctx->h_stage[i]) (void)hipHostFree(ctx->h_stage[i]); if (ctx->h_stage_ev[i]) (void)hipEventDestroy(ctx->h_stage_ev[i]); }
@@ -2348,3 +2349,4 @@ int tcr_round_graph_stats(tcr_ctx *ctx, int64_t *n_graphs, int64_t *n_replays)
 #include "tcr_windfield.hip"             // wind footprint (peak wind at sites from a radial profile, exceedance counts)
 #include "tcr_loss.hip"                  // portfolio loss (damage function on the footprint, summed over sites inside the scan)
 #include "tcr_rainfall.hip"              // rainfall footprint (R-CLIPER rain rate integrated along the track, or its peak, at sites)
+#include "tcr_compound.hip"              // compound wind-rain hazard (both footprints in one scan, joint exceedance counts)

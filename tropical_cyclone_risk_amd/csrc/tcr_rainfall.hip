@@ -65,6 +65,20 @@ __device__ __forceinline__ RfRec rf_record(const RfPrepArgs &a, double x, double
     return r;
 }
 
+// record q of the nr records of a track (planes at the storm's row): sample q / sub, or the sub-sample at tau = (q % sub) / sub
+// after it, with the trapezoid weight of its place in the track
+__device__ __forceinline__ RfRec rf_sub_record(const RfPrepArgs &a, const double *lon, const double *lat, const double *vv, int q, int nr)
+{
+    const int k = q / a.sub, j = q - k * a.sub;
+    const double w = (q == 0 || q == nr - 1) ? 0.5 * a.w : a.w;
+    const double x = lon[k], y = lat[k], v = vv[k];
+    if (j == 0) return rf_record(a, x, y, v, w);
+    const double tau = (double)j / (double)a.sub;
+    double dl = lon[k + 1] - x;
+    dl -= 360.0 * floor((dl + 180.0) / 360.0);          // [-180, 180)
+    return rf_record(a, x + tau * dl, y + tau * (lat[k + 1] - y), v + tau * (vv[k + 1] - v), w);
+}
+
 __global__ __launch_bounds__(64) void k_rain_prep(RfPrepArgs a)
 {
     const int64_t s = blockIdx.x;
@@ -72,26 +86,10 @@ __global__ __launch_bounds__(64) void k_rain_prep(RfPrepArgs a)
     const int64_t o = s * a.stride;
     const double *lon = a.lon + o, *lat = a.lat + o, *vv = a.vmax + o;
     // the track: the samples before the first one with a non-finite input
-    int64_t n = a.n_t;
-    for (int64_t j0 = 0; j0 < a.n_t; j0 += 64) {
-        const int64_t j = j0 + lane;
-        bool bad = false;
-        if (j < a.n_t) bad = !(isfinite(lon[j]) && isfinite(lat[j]) && isfinite(vv[j]));
-        const unsigned long long m = __ballot(bad);
-        if (m) { n = j0 + __ffsll((long long)m) - 1; break; }
-    }
+    const int64_t n = scan_track_len(a.n_t, [&](int64_t j) { return !(isfinite(lon[j]) && isfinite(lat[j]) && isfinite(vv[j])); });
     RfRec *row = a.out.rec + s * a.out.n_seg_max * kHzSeg;
     const int nr = n >= 2 ? (int)((n - 1) * a.sub + 1) : 0;
-    for (int q = lane; q < nr; q += 64) {
-        const int k = q / a.sub, j = q - k * a.sub;
-        const double w = (q == 0 || q == nr - 1) ? 0.5 * a.w : a.w;
-        const double x = lon[k], y = lat[k], v = vv[k];
-        if (j == 0) { row[q] = rf_record(a, x, y, v, w); continue; }
-        const double tau = (double)j / (double)a.sub;
-        double dl = lon[k + 1] - x;
-        dl -= 360.0 * floor((dl + 180.0) / 360.0);      // [-180, 180)
-        row[q] = rf_record(a, x + tau * dl, y + tau * (lat[k + 1] - y), v + tau * (vv[k + 1] - v), w);
-    }
+    for (int q = lane; q < nr; q += 64) row[q] = rf_sub_record(a, lon, lat, vv, q, nr);
     scan_finish_row(a.out, s, nr);
 }
 
@@ -102,9 +100,11 @@ struct RainScan {
     using Rec = RfRec;
     static constexpr int kUnroll = 2;
     static constexpr bool kSum = SUM;
-    __device__ __forceinline__ double value(const ScanSite &, const RfRec &p, double q) const
+    __device__ __forceinline__ double value(const ScanSite &s, const RfRec &p, double q) const { return at_angle(s, p, scan_pair_angle(q)); }
+    // the same from the pair's angle (radians), which a joint scan (tcr_compound.hip) forms once for two hazards
+    __device__ __forceinline__ double at_angle(const ScanSite &, const RfRec &p, double ang) const
     {
-        const double r = (2.0 * asin(sqrt(q))) * (kWfEarthR / 1000.0);
+        const double r = ang * (kWfEarthR / 1000.0);
         const double rate = fmax(r < p.rm ? p.t0 + p.slope * r : p.tm * exp(-(r - p.rm) * p.ire), 0.0);
         return SUM ? p.w * rate : rate;
     }
@@ -113,27 +113,28 @@ struct RainScan {
 // U of a clamp end (knots)
 inline double rf_u(double kt) { return 1.0 + (kt - 35.0) / 33.0; }
 
+// who: the prefix of the messages (tcr_compound.hip runs the same rules under its own name)
 int rainfall_check(tcr_ctx *ctx, const tcr_hazard_tracks *t, const tcr_rain_params *p, int64_t n_site, const double *site_lon,
-                   const double *site_lat, int32_t n_bin, const double *thr, const int32_t *counts)
+                   const double *site_lat, int32_t n_bin, const double *thr, const int32_t *counts, const char *who = "tcr_rainfall")
 {
     if (!t || !p || !site_lon || !site_lat || !thr || !counts || !t->lon || !t->lat || !t->vmax || !t->group_off)
-        return fail(ctx, "tcr_rainfall: NULL argument");
-    if (!(p->dt_s > 0.0 && std::isfinite(p->dt_s))) return fail(ctx, "tcr_rainfall: dt_s must be finite and > 0");
-    if (!(p->r_out_km > 0.0 && p->r_out_km <= 2000.0)) return fail(ctx, "tcr_rainfall: r_out_km must be in (0, 2000]");
-    if (p->substeps < 1 || p->substeps > kRfMaxSub) return fail(ctx, "tcr_rainfall: substeps must be in [1, 64]");
+        return fail(ctx, "%s: NULL argument", who);
+    if (!(p->dt_s > 0.0 && std::isfinite(p->dt_s))) return fail(ctx, "%s: dt_s must be finite and > 0", who);
+    if (!(p->r_out_km > 0.0 && p->r_out_km <= 2000.0)) return fail(ctx, "%s: r_out_km must be in (0, 2000]", who);
+    if (p->substeps < 1 || p->substeps > kRfMaxSub) return fail(ctx, "%s: substeps must be in [1, 64]", who);
     if (p->stat != TCR_RAIN_TOTAL && p->stat != TCR_RAIN_PEAK_RATE)
-        return fail(ctx, "tcr_rainfall: stat must be TCR_RAIN_TOTAL (0) or TCR_RAIN_PEAK_RATE (1)");
+        return fail(ctx, "%s: stat must be TCR_RAIN_TOTAL (0) or TCR_RAIN_PEAK_RATE (1)", who);
     if (!(p->v_lo_kt > 0.0 && p->v_lo_kt <= p->v_hi_kt && std::isfinite(p->v_hi_kt)))
-        return fail(ctx, "tcr_rainfall: need 0 < v_lo_kt <= v_hi_kt, both finite");
+        return fail(ctx, "%s: need 0 < v_lo_kt <= v_hi_kt, both finite", who);
     for (int i = 0; i < 4; ++i)
-        if (!(std::isfinite(p->a[i]) && std::isfinite(p->b[i]))) return fail(ctx, "tcr_rainfall: the coefficients must be finite");
+        if (!(std::isfinite(p->a[i]) && std::isfinite(p->b[i]))) return fail(ctx, "%s: the coefficients must be finite", who);
     // Tm, rm and re are linear in U: what holds at both clamp ends holds in between
     for (const double kt : {p->v_lo_kt, p->v_hi_kt}) {
         const double u = rf_u(kt);
         if (!(p->a[2] + p->b[2] * u > 0.0 && p->a[3] + p->b[3] * u > 0.0 && p->a[1] + p->b[1] * u >= 0.0))
-            return fail(ctx, "tcr_rainfall: the coefficients must give rm > 0, re > 0 and Tm >= 0 at v_lo_kt and at v_hi_kt");
+            return fail(ctx, "%s: the coefficients must give rm > 0, re > 0 and Tm >= 0 at v_lo_kt and at v_hi_kt", who);
     }
-    return scan_check(ctx, "tcr_rainfall", t, 1 << 20, "1 <= n_t <= 2^20", n_site, n_bin, thr);
+    return scan_check(ctx, who, t, 1 << 20, "1 <= n_t <= 2^20", n_site, n_bin, thr);
 }
 
 }  // namespace

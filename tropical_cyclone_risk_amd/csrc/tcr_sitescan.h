@@ -1,5 +1,5 @@
-// The site scan: what the per-site analyses of a track ensemble (tcr_hazard.hip, tcr_windfield.hip, tcr_loss.hip, tcr_rainfall.hip)
-// share.  Each of them turns
+// The site scan: what the per-site analyses of a track ensemble (tcr_hazard.hip, tcr_windfield.hip, tcr_loss.hip, tcr_rainfall.hip,
+// tcr_compound.hip) share.  Each of them turns
 // every storm into a row of wave-uniform records, and wants
 //
 //   site_max[site][storm] = max of value(site, record) over the storm's records with haversine(site, record) <= R   (NaN: none)
@@ -22,8 +22,21 @@
 //                   site_max[site][storm] = sum of value(site, record) over the same records, in record order (NaN: none).  The
 //                   first included record replaces the NaN start, every later one is added to it: nothing is ever added to a NaN.
 //                   kSum with kLoss is a static_assert.  Policies without kSum compile to the code they had before it existed.
-// and calls scan_run with a workspace of its own (ScanWs, four instances in tcr_ctx: a hazard, a footprint, a loss and a rainfall
-// call may be in flight on different streams of one context).
+//                   A policy with `static constexpr bool kJoint = true` (tcr_compound.hip) scans two hazards of one record at
+//                   once: the pair's angle is formed once, first(site, record, angle) goes into a max under the policy's a_first and
+//                   second(site, record, angle) into a max, or with kSecondSum into a sum in record order, under its a_second;
+//                   a_R and r_ang (the culling) are those of the larger radius.  site_max takes the first, the policy's
+//                   site_second the second.  thr holds the n_first thresholds of the first, then the n_second of the second, and
+//                   the histogram is two-dimensional: n_bin = (n_first + 1) (n_second + 1) and
+//                   counts[site][group][a (n_second + 1) + b] = #storms of the group passing at least a thresholds of the first and
+//                   at least b of the second (a NaN passes none, so index 0 is "no condition" and [0][0] the size of the group).
+//                   A wave's histogram is its LDS, and 64 cells of int32 per lane (16 KB) leave room for 9 waves on a CU: the
+//                   joint scan ran at 2 waves / SIMD and 1.6 x slower than with 9 cells (profiles/compound_bench.txt).  So the
+//                   joint histogram's cells are kJointHist (16 bits), and the caller keeps a chunk at kJointMaxChunk storms or
+//                   fewer (scan_run's max_chunk), which no cell and no suffix sum can exceed.
+//                   kJoint with kLoss or kSum is a static_assert.  Policies without kJoint compile to the code they had before it.
+// and calls scan_run with a workspace of its own (ScanWs, five instances in tcr_ctx: a hazard, a footprint, a loss, a rainfall and
+// a compound call may be in flight on different streams of one context).
 //
 //   k_site_scan      one wave per (tile of 64 sites, chunk of storms of one group): every lane holds one site's terms in registers;
 //                    the records are wave-uniform and come through scalar loads.  A storm or segment whose cap is farther than R
@@ -42,11 +55,19 @@
 // the storm is in and which other storms and sites the call has change which segments are culled, never the terms or their order.
 // So the sum is bit-identical whatever the launch shape, the site order and the storm order.  This rests on site_max being written
 // by the one lane that accumulated it: no cross-lane or cross-chunk reduction may ever touch it.
+//
+// And for a kJoint policy.  Each of its two accumulators sees exactly the records with a <= its own a threshold, in record order,
+// and nothing else: the cull uses the larger radius, so it is conservative for both; the test of one hazard never gates the other;
+// the values come from the functions the single-hazard policies call, on the same record terms and the same angle expression.  So
+// each plane is bit for bit what the single-hazard scan of that policy writes, and the 2-D counts are integer sums of per-storm
+// ranks of those values: bit-identical whatever the launch shape, the site order and the storm order.
 
 namespace {
 
 constexpr int kHzSeg = 32;                  // records per culling segment
 constexpr int kHzMaxBin = 64;
+using kJointHist = uint16_t;                // a cell of the joint scan's LDS histogram
+constexpr int64_t kJointMaxChunk = 65535;   // storms of a chunk it can count
 constexpr double kHzPad = 1e-9;             // radians added to every cap radius
 constexpr double kHzDotPad = 1e-12;         // cosine-space margin of the cap test
 
@@ -98,6 +119,8 @@ __device__ __forceinline__ double hz_a(double sp1, double cp1, double sl1, doubl
 }
 
 __device__ __forceinline__ double hz_angle(double a) { return 2.0 * asin(sqrt(fmin(fmax(a, 0.0), 1.0))); }
+// the angle (radians) of an included pair from its haversine argument, as the profile policies use it (a <= a_R < 1: no clamp)
+__device__ __forceinline__ double scan_pair_angle(double a) { return 2.0 * asin(sqrt(a)); }
 
 __device__ __forceinline__ double wave_max(double x)
 {
@@ -123,6 +146,33 @@ template <class P, class = void>
 struct scan_has_sum : std::false_type {};
 template <class P>
 struct scan_has_sum<P, std::void_t<decltype(P::kSum)>> : std::bool_constant<P::kSum> {};
+
+// Policy::kJoint when the policy has one, false otherwise
+template <class P, class = void>
+struct scan_has_joint : std::false_type {};
+template <class P>
+struct scan_has_joint<P, std::void_t<decltype(P::kJoint)>> : std::bool_constant<P::kJoint> {};
+
+// the number of the n ascending thresholds thr that are <= m (0 for a NaN: no comparison holds): the joint scan's two ranks
+__device__ __forceinline__ int scan_rank(const double *thr, int n, double m)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (thr[mid] <= m) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+// The track of a prep kernel (one wave): the number of samples before the first j in [0, n_t) with bad(j), n_t when there is none.
+template <class Bad>
+__device__ __forceinline__ int64_t scan_track_len(int64_t n_t, Bad bad)
+{
+    const int lane = threadIdx.x;
+    for (int64_t j0 = 0; j0 < n_t; j0 += 64) {
+        const int64_t j = j0 + lane;
+        const unsigned long long m = __ballot(j < n_t && bad(j));
+        if (m) return j0 + __ffsll((long long)m) - 1;
+    }
+    return n_t;
+}
 
 // cap (centre = the record at `mid`, radius = the largest angle from it) of the records [b, e) of one row
 template <class Rec>
@@ -171,7 +221,11 @@ template <class Policy>
 __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec> a, Policy pol)
 {
     using Rec = typename Policy::Rec;
-    extern __shared__ int32_t hist[];                   // [n_bin + 1][64]: storms of this lane whose max passes exactly k thresholds
+    // [n_bin + 1][64]: storms of this lane whose max passes exactly k thresholds (kJoint: [n_first + 1][n_second + 1][64] cells of
+    // kJointHist, exactly (kw, kr) of each list)
+    using Hist = std::conditional_t<scan_has_joint<Policy>::value, kJointHist, int32_t>;
+    extern __shared__ int32_t hist_lds[];
+    Hist *hist = reinterpret_cast<Hist *>(hist_lds);
     const int lane = threadIdx.x;
     const int64_t tile = blockIdx.x % a.n_tile, chunk = blockIdx.x / a.n_tile;
     const int64_t site = tile * 64 + lane;
@@ -197,11 +251,14 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
     constexpr bool kLoss = scan_has_loss<Policy>::value;
     constexpr bool kSum = scan_has_sum<Policy>::value;
     static_assert(!(kSum && kLoss), "the loss variant of the scan is defined on a max");
+    constexpr bool kJoint = scan_has_joint<Policy>::value;
+    static_assert(!(kJoint && (kLoss || kSum)), "the joint scan has accumulators of its own: neither the loss nor the sum variant");
     [[maybe_unused]] double loss_acc = 0.0;             // kLoss: this site's losses of the chunk's storms, summed in storm order
     [[maybe_unused]] auto terms = [&] { if constexpr (kLoss) return pol.site_terms(my, valid); else return 0; }();
     __syncthreads();
     for (int64_t s = s_begin; s < s_end; ++s) {
         double m = NAN;
+        [[maybe_unused]] double m2 = NAN;               // kJoint: the second hazard
         [[maybe_unused]] bool near = false;             // kLoss: the storm's cap reaches the tile (wave-uniform)
         const int n = hz_uniform(a.rows.cnt + s);
         if (n > 0 && !hz_far(hz_uniform(a.rows.storm + s), tx, ty, tz, ct, st, rt)) {
@@ -216,7 +273,17 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
                 for (int j = 0; j < kHzSeg; ++j) {                  // (padding records fail the test: NaN terms)
                     const Rec p = Rec::uniform(seg + j);
                     const double q = hz_a(me.sp, me.cp, me.sl, me.cl, me.cosp, p.sp, p.cp, p.sl, p.cl, p.cosp);
-                    if constexpr (kSum) {
+                    if constexpr (kJoint) {
+                        if (q <= a.a_R) {                           // the larger radius; then each hazard under its own
+                            const double ang = scan_pair_angle(q);
+                            if (q <= pol.a_first) m = fmax(m, pol.first(me, p, ang));
+                            if (q <= pol.a_second) {
+                                const double v = pol.second(me, p, ang);
+                                if constexpr (Policy::kSecondSum) m2 = isnan(m2) ? v : m2 + v;          // in record order
+                                else m2 = fmax(m2, v);
+                            }
+                        }
+                    } else if constexpr (kSum) {
                         if (q <= a.a_R) { const double v = pol.value(me, p, q); m = isnan(m) ? v : m + v; }   // in record order
                     } else {
                         if (q <= a.a_R) m = fmax(m, pol.value(me, p, q));   // fmax skips NaN: the start, or a NaN value
@@ -225,6 +292,9 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
             }
         }
         if (a.site_max && valid) a.site_max[site * a.n_trk + s] = m;
+        if constexpr (kJoint) {
+            if (pol.site_second && valid) pol.site_second[site * a.n_trk + s] = m2;
+        }
         if constexpr (kLoss) {
             double t = 0.0;                             // a storm culled for the whole tile: 0, without the butterfly
             if (near) {
@@ -234,16 +304,31 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
             }
             if (lane == 0) pol.tile_loss[tile * a.n_trk + s] = t;
         }
-        if (!isnan(m)) {
+        if constexpr (kJoint) {                         // every storm is counted: a NaN has rank 0
+            const int kw = scan_rank(a.thr, pol.n_first, m), kr = scan_rank(a.thr + pol.n_first, pol.n_second, m2);
+            hist[(kw * (pol.n_second + 1) + kr) * 64 + lane] += 1;
+        } else if (!isnan(m)) {
             int lo = 0, hi = a.n_bin;                   // k = #thresholds <= m
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (a.thr[mid] <= m) lo = mid + 1; else hi = mid; }
             hist[lo * 64 + lane] += 1;
         }
     }
+    if constexpr (kJoint) {
+        // exactly (kw, kr) -> at least (kw, kr): suffix sums along the second axis, then along the first, in the lane's own column
+        const int nw = pol.n_first, nr = pol.n_second;
+        for (int kw = nw; kw >= 0; --kw)
+            for (int kr = nr - 1; kr >= 0; --kr) hist[(kw * (nr + 1) + kr) * 64 + lane] += hist[(kw * (nr + 1) + kr + 1) * 64 + lane];
+        for (int kw = nw - 1; kw >= 0; --kw)
+            for (int kr = nr; kr >= 0; --kr) hist[(kw * (nr + 1) + kr) * 64 + lane] += hist[((kw + 1) * (nr + 1) + kr) * 64 + lane];
+    }
     if (valid) {
-        int32_t c = 0;
+        [[maybe_unused]] int32_t c = 0;
         int32_t *out = a.part + (chunk * a.n_site + site) * a.n_bin;
-        for (int b = a.n_bin - 1; b >= 0; --b) { c += hist[(b + 1) * 64 + lane]; out[b] = c; }
+        if constexpr (kJoint) {
+            for (int b = 0; b < a.n_bin; ++b) out[b] = hist[b * 64 + lane];
+        } else {
+            for (int b = a.n_bin - 1; b >= 0; --b) { c += hist[(b + 1) * 64 + lane]; out[b] = c; }
+        }
         if constexpr (kLoss) pol.site_part[chunk * a.n_site + site] = loss_acc;
     }
     if (lane == 0 && pairs) atomicAdd(a.pairs, pairs * n_lanes);
@@ -293,12 +378,13 @@ int scan_check(tcr_ctx *ctx, const char *who, const Tracks *t, int64_t n_t_max, 
 }
 
 // chunks: every group split into pieces of at most `ch` storms, sized so that the grid has ~8192 waves.  tab: [n_chunk][3] storm
-// begin, storm end, group; gch: [n_group + 1] the first chunk of every group.  A function of the group offsets and n_tile alone.
+// begin, storm end, group; gch: [n_group + 1] the first chunk of every group.  A function of the group offsets and n_tile alone,
+// and of max_chunk, the most storms a chunk may hold.
 template <class Tracks>
-void scan_chunks(const Tracks *t, int64_t n_tile, std::vector<int64_t> &tab, std::vector<int64_t> &gch)
+void scan_chunks(const Tracks *t, int64_t n_tile, std::vector<int64_t> &tab, std::vector<int64_t> &gch, int64_t max_chunk = INT64_MAX)
 {
     const int64_t want = std::max<int64_t>(1, (8192 + n_tile - 1) / n_tile);
-    const int64_t ch = std::max<int64_t>(16, (t->n_trk + want - 1) / want);
+    const int64_t ch = std::min(max_chunk, std::max<int64_t>(16, (t->n_trk + want - 1) / want));
     tab.clear(); gch.assign(1, 0);
     for (int64_t g = 0; g < t->n_group; ++g) {
         for (int64_t b = t->group_off[g]; b < t->group_off[g + 1]; b += ch) {
@@ -308,19 +394,28 @@ void scan_chunks(const Tracks *t, int64_t n_tile, std::vector<int64_t> &tab, std
     }
 }
 
+// the haversine argument sin^2(angle / 2) of radius_km on a sphere of re_km: what a pair's a is tested against
+inline double scan_a_of(double radius_km, double re_km)
+{
+    const double h = sin(radius_km / (2.0 * re_km));
+    return h * h;
+}
+
 // One call on stream st: chunk table, workspaces, launch, reduction.  launch(args, workspace 5, grid, LDS bytes) enqueues the
 // analysis's prep kernel, then its k_site_scan instantiation, and returns the first launch error.  n_rec: the most records a
-// storm can have; radius_km on a sphere of re_km; extra_bytes: what the prep kernel wants in workspace 5.
+// storm can have; radius_km on a sphere of re_km; extra_bytes: what the prep kernel wants in workspace 5.  A kJoint policy's call
+// passes n_bin = (n_first + 1) (n_second + 1), kHzMaxBin thresholds (its two lists, then anything), the larger radius and
+// max_chunk = kJointMaxChunk, and launches with LDS for kJointHist cells instead of the int32 bytes it is handed.
 template <class Rec, class Tracks, class Launch>
 int scan_run(tcr_ctx *ctx, ScanWs &w, const char *who, const Tracks *t, int64_t n_rec, size_t extra_bytes, int64_t n_site,
              const double *site_lon, const double *site_lat, double radius_km, double re_km, int32_t n_bin, const double *thresholds,
-             int32_t *counts, double *site_max, hipStream_t st, Launch launch)
+             int32_t *counts, double *site_max, hipStream_t st, Launch launch, int64_t max_chunk = INT64_MAX)
 {
     const int64_t n_trk = t->n_trk, n_group = t->n_group;
     const int64_t n_tile = (n_site + 63) / 64, n_seg_max = (n_rec + kHzSeg - 1) / kHzSeg;
 
     std::vector<int64_t> tab, gch;
-    scan_chunks(t, n_tile, tab, gch);
+    scan_chunks(t, n_tile, tab, gch, max_chunk);
     const int64_t n_chunk = (int64_t)tab.size() / 3;
     if (n_tile * n_chunk >= ((int64_t)1 << 31) || n_site * n_group * n_bin >= ((int64_t)1 << 39))
         return fail(ctx, "%s: too many sites x storm chunks for one launch; split the sites", who);
@@ -362,8 +457,7 @@ int scan_run(tcr_ctx *ctx, ScanWs &w, const char *who, const Tracks *t, int64_t 
         m.chunks = d_tab;
         m.site_lon = site_lon; m.site_lat = site_lat;
         m.n_site = n_site; m.n_tile = n_tile; m.n_trk = n_trk;
-        const double h = sin(radius_km / (2.0 * re_km));
-        m.a_R = h * h; m.r_ang = radius_km / re_km;
+        m.a_R = scan_a_of(radius_km, re_km); m.r_ang = radius_km / re_km;
         m.n_bin = n_bin;
         for (int b = 0; b < n_bin; ++b) m.thr[b] = thresholds[b];
         m.part = part; m.site_max = site_max; m.pairs = d_pairs;

@@ -111,58 +111,58 @@ __device__ __forceinline__ WfRec wf_record(double x, double y, double v, double 
     return r;
 }
 
+// the stage entry of sample k of a track of n >= 2 samples that begins at offset o of the planes: position, intensity, rm and A, with
+// the neighbour and end-extrapolation rules of k_emit; bad_rm is set when rm is not finite and > 0
+__device__ __forceinline__ WfStage wf_stage(const WfPrepArgs &a, int64_t o, int64_t k, int64_t n, bool &bad_rm)
+{
+    const double *lon = a.lon + o, *lat = a.lat + o;
+    const double x = lon[k], y = lat[k], v = a.v[o + k];
+    double lom = 0.0, lam = 0.0, lop = 0.0, lap = 0.0;
+    if (k > 0) { lom = lon[k - 1]; lam = lat[k - 1]; }
+    if (k < n - 1) { lop = lon[k + 1]; lap = lat[k + 1]; }
+    const double lop_in = lop, lap_in = lap, lom_in = lom, lam_in = lam;
+    if (k == 0) { lom = 2.0 * x - lop_in; lam = 2.0 * y - lap_in; }
+    if (k == n - 1) { lop = 2.0 * x - lom_in; lap = 2.0 * y - lam_in; }
+    double ae, an;
+    wf_asym(a.dt, y, v, a.u250[o + k] - a.u850[o + k], a.v250[o + k] - a.v850[o + k], lom, lam, lop, lap, ae, an);
+    const double rm = a.rmax ? a.rmax[o + k] : (a.rm_const > 0.0 ? a.rm_const : 46.4 * exp(-0.0155 * v + 0.0169 * fabs(y)));
+    if (!(isfinite(rm) && rm > 0.0)) bad_rm = true;
+    return WfStage{x, y, v, rm, ae, an, 0.0, 0.0};
+}
+
+// record q of a staged track: sample q / sub, or the sub-sample at tau = (q % sub) / sub after it
+__device__ __forceinline__ WfRec wf_sub_record(const WfStage *st, int q, int sub)
+{
+    const int k = q / sub, j = q - k * sub;
+    const WfStage p = st[k];
+    if (j == 0) return wf_record(p.lon, p.lat, p.v, p.rm, p.ae, p.an);
+    const WfStage p1 = st[k + 1];
+    const double tau = (double)j / (double)sub;
+    double dl = p1.lon - p.lon;
+    dl -= 360.0 * floor((dl + 180.0) / 360.0);          // [-180, 180)
+    return wf_record(p.lon + tau * dl, p.lat + tau * (p1.lat - p.lat), p.v + tau * (p1.v - p.v), p.rm + tau * (p1.rm - p.rm),
+                     p.ae + tau * (p1.ae - p.ae), p.an + tau * (p1.an - p.an));
+}
+
 __global__ __launch_bounds__(64) void k_wind_prep(WfPrepArgs a)
 {
     const int64_t s = blockIdx.x;
     const int lane = threadIdx.x;
     const int64_t o = s * a.stride;
-    const double *lon = a.lon + o, *lat = a.lat + o, *vv = a.v + o;
-    const double *u2 = a.u250 + o, *v2 = a.v250 + o, *u8 = a.u850 + o, *v8 = a.v850 + o;
     // the track: the samples before the first one with a non-finite input
-    int64_t n = a.n_t;
-    for (int64_t j0 = 0; j0 < a.n_t; j0 += 64) {
-        const int64_t j = j0 + lane;
-        bool bad = false;
-        if (j < a.n_t)
-            bad = !(isfinite(lon[j]) && isfinite(lat[j]) && isfinite(vv[j]) && isfinite(u2[j]) && isfinite(v2[j]) && isfinite(u8[j]) &&
-                    isfinite(v8[j]));
-        const unsigned long long m = __ballot(bad);
-        if (m) { n = j0 + __ffsll((long long)m) - 1; break; }
-    }
+    const int64_t n = scan_track_len(a.n_t, [&](int64_t j) {
+        return !(isfinite(a.lon[o + j]) && isfinite(a.lat[o + j]) && isfinite(a.v[o + j]) && isfinite(a.u250[o + j]) &&
+                 isfinite(a.v250[o + j]) && isfinite(a.u850[o + j]) && isfinite(a.v850[o + j]));
+    });
     WfStage *st = a.stage + s * a.n_t;
     WfRec *row = a.out.rec + s * a.out.n_seg_max * kHzSeg;
-    // per sample: position, intensity, rm and A, with the neighbour and end-extrapolation rules of k_emit
     bool bad_rm = false;
-    if (n >= 2) {
-        for (int64_t k = lane; k < n; k += 64) {
-            const double x = lon[k], y = lat[k], v = vv[k];
-            double lom = 0.0, lam = 0.0, lop = 0.0, lap = 0.0;
-            if (k > 0) { lom = lon[k - 1]; lam = lat[k - 1]; }
-            if (k < n - 1) { lop = lon[k + 1]; lap = lat[k + 1]; }
-            const double lop_in = lop, lap_in = lap, lom_in = lom, lam_in = lam;
-            if (k == 0) { lom = 2.0 * x - lop_in; lam = 2.0 * y - lap_in; }
-            if (k == n - 1) { lop = 2.0 * x - lom_in; lap = 2.0 * y - lam_in; }
-            double ae, an;
-            wf_asym(a.dt, y, v, u2[k] - u8[k], v2[k] - v8[k], lom, lam, lop, lap, ae, an);
-            const double rm = a.rmax ? a.rmax[o + k] : (a.rm_const > 0.0 ? a.rm_const : 46.4 * exp(-0.0155 * v + 0.0169 * fabs(y)));
-            if (!(isfinite(rm) && rm > 0.0)) bad_rm = true;
-            st[k] = WfStage{x, y, v, rm, ae, an, 0.0, 0.0};
-        }
-    }
+    if (n >= 2)
+        for (int64_t k = lane; k < n; k += 64) st[k] = wf_stage(a, o, k, n, bad_rm);
     const bool drop = __ballot(bad_rm) != 0;
     const int nr = (n >= 2 && !drop) ? (int)((n - 1) * a.sub + 1) : 0;
     __syncthreads();                                    // the records read stage entries other lanes wrote
-    for (int q = lane; q < nr; q += 64) {
-        const int k = q / a.sub, j = q - k * a.sub;
-        const WfStage p = st[k];
-        if (j == 0) { row[q] = wf_record(p.lon, p.lat, p.v, p.rm, p.ae, p.an); continue; }
-        const WfStage p1 = st[k + 1];
-        const double tau = (double)j / (double)a.sub;
-        double dl = p1.lon - p.lon;
-        dl -= 360.0 * floor((dl + 180.0) / 360.0);      // [-180, 180)
-        row[q] = wf_record(p.lon + tau * dl, p.lat + tau * (p1.lat - p.lat), p.v + tau * (p1.v - p.v), p.rm + tau * (p1.rm - p.rm),
-                           p.ae + tau * (p1.ae - p.ae), p.an + tau * (p1.an - p.an));
-    }
+    for (int q = lane; q < nr; q += 64) row[q] = wf_sub_record(st, q, a.sub);
     scan_finish_row(a.out, s, nr);
 }
 
@@ -172,9 +172,11 @@ struct WindScan {
     using Rec = WfRec;
     static constexpr int kUnroll = 2;
     double c, two_c, inv_exp;               // profile: c, 2 - c, 1 / (2 - c)
-    __device__ __forceinline__ double value(const ScanSite &s, const WfRec &p, double q) const
+    __device__ __forceinline__ double value(const ScanSite &s, const WfRec &p, double q) const { return at_angle(s, p, scan_pair_angle(q)); }
+    // the same from the pair's angle (radians), which a joint scan (tcr_compound.hip) forms once for two hazards
+    __device__ __forceinline__ double at_angle(const ScanSite &s, const WfRec &p, double ang) const
     {
-        const double r = (2.0 * asin(sqrt(q))) * kWfEarthR;
+        const double r = ang * kWfEarthR;
         double V;
         if (UNIT_C) {
             V = r * (2.0 * p.mm / (p.rm * p.rm + r * r) - p.f2);
@@ -191,19 +193,20 @@ struct WindScan {
     }
 };
 
+// who: the prefix of the messages (tcr_compound.hip runs the same rules under its own name)
 int windfield_check(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params *p, int64_t n_site, const double *site_lon,
-                    const double *site_lat, int32_t n_bin, const double *thr, const int32_t *counts)
+                    const double *site_lat, int32_t n_bin, const double *thr, const int32_t *counts, const char *who = "tcr_windfield")
 {
     if (!t || !p || !site_lon || !site_lat || !thr || !counts || !t->lon || !t->lat || !t->v || !t->u250 || !t->v250 || !t->u850 ||
         !t->v850 || !t->group_off)
-        return fail(ctx, "tcr_windfield: NULL argument");
-    if (!(p->dt_s > 0.0 && std::isfinite(p->dt_s))) return fail(ctx, "tcr_windfield: dt_s must be finite and > 0");
-    if (!(p->ck_cd > 0.0 && p->ck_cd < 2.0)) return fail(ctx, "tcr_windfield: ck_cd must be in (0, 2)");
-    if (!(p->r_out_km > 0.0 && p->r_out_km <= 2000.0)) return fail(ctx, "tcr_windfield: r_out_km must be in (0, 2000]");
-    if (p->substeps < 1 || p->substeps > kWfMaxSub) return fail(ctx, "tcr_windfield: substeps must be in [1, 64]");
+        return fail(ctx, "%s: NULL argument", who);
+    if (!(p->dt_s > 0.0 && std::isfinite(p->dt_s))) return fail(ctx, "%s: dt_s must be finite and > 0", who);
+    if (!(p->ck_cd > 0.0 && p->ck_cd < 2.0)) return fail(ctx, "%s: ck_cd must be in (0, 2)", who);
+    if (!(p->r_out_km > 0.0 && p->r_out_km <= 2000.0)) return fail(ctx, "%s: r_out_km must be in (0, 2000]", who);
+    if (p->substeps < 1 || p->substeps > kWfMaxSub) return fail(ctx, "%s: substeps must be in [1, 64]", who);
     if (!(p->rmax_const_km >= 0.0 && std::isfinite(p->rmax_const_km)) || (t->rmax_km && p->rmax_const_km != 0.0))
-        return fail(ctx, "tcr_windfield: rmax_const_km must be finite and >= 0, and 0 when the rmax_km plane is given");
-    return scan_check(ctx, "tcr_windfield", t, 1 << 20, "1 <= n_t <= 2^20", n_site, n_bin, thr);
+        return fail(ctx, "%s: rmax_const_km must be finite and >= 0, and 0 when the rmax_km plane is given", who);
+    return scan_check(ctx, who, t, 1 << 20, "1 <= n_t <= 2^20", n_site, n_bin, thr);
 }
 
 // The launch step of scan_run for every analysis on the footprint's records: the footprint's prep kernel, then Policy's scan.
@@ -214,6 +217,27 @@ hipError_t wind_scan_launch(const tcr_wind_tracks *t, const tcr_wind_params *prm
     WfPrepArgs p{t->lon, t->lat, t->v, t->u250, t->v250, t->u850, t->v850, t->rmax_km, t->n_trk, t->n_t, t->row_stride,
                  prm->dt_s, prm->rmax_const_km, prm->substeps, static_cast<WfStage *>(stage), m.rows};
     return scan_launch(k_wind_prep, p, t->n_trk, m, grid, lds, st, pol);
+}
+
+// What a _host entry point checks and a _dev one cannot report: the rmax_km plane (when given) is finite and > 0 at every sample
+// of a track (host planes)
+bool wind_rmax_ok(const tcr_wind_tracks *t)
+{
+    if (!t->rmax_km) return true;
+    const double *planes[7] = {t->lon, t->lat, t->v, t->u250, t->v250, t->u850, t->v850};
+    for (int64_t s = 0; s < t->n_trk; ++s) {
+        const int64_t o = s * t->row_stride;
+        int64_t n = 0;
+        while (n < t->n_t) {
+            bool ok = true;
+            for (const double *p : planes) ok = ok && std::isfinite(p[o + n]);
+            if (!ok) break;
+            ++n;
+        }
+        for (int64_t k = 0; n >= 2 && k < n; ++k)
+            if (!(std::isfinite(t->rmax_km[o + k]) && t->rmax_km[o + k] > 0.0)) return false;
+    }
+    return true;
 }
 
 // For a _host entry point on tcr_wind_tracks: *d = *t with the seven planes (eight with rmax_km) on the device (B owns them).  No
@@ -255,23 +279,7 @@ int tcr_windfield_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_pa
 {
     if (!ctx) return -1;
     if (windfield_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
-    // rm > 0 and finite at every sample of a track (the device entry point cannot report it)
-    if (t->rmax_km) {
-        const double *planes[7] = {t->lon, t->lat, t->v, t->u250, t->v250, t->u850, t->v850};
-        for (int64_t s = 0; s < t->n_trk; ++s) {
-            const int64_t o = s * t->row_stride;
-            int64_t n = 0;
-            while (n < t->n_t) {
-                bool ok = true;
-                for (const double *p : planes) ok = ok && std::isfinite(p[o + n]);
-                if (!ok) break;
-                ++n;
-            }
-            for (int64_t k = 0; n >= 2 && k < n; ++k)
-                if (!(std::isfinite(t->rmax_km[o + k]) && t->rmax_km[o + k] > 0.0))
-                    return fail(ctx, "tcr_windfield_host: rmax_km must be finite and > 0 at every sample of a track");
-        }
-    }
+    if (!wind_rmax_ok(t)) return fail(ctx, "tcr_windfield_host: rmax_km must be finite and > 0 at every sample of a track");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
     tcr_wind_tracks d;

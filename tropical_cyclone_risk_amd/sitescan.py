@@ -1,6 +1,6 @@
-"""The Python side of the per-site scan (csrc/tcr_sitescan.h), which site hazard, wind footprint and portfolio loss share: the
-checks of sites and groups, the order the kernel wants (the storms of a group next to each other, the sites in Z-order), the
-call, and the way back to the caller's site and storm order."""
+"""The Python side of the per-site scan (csrc/tcr_sitescan.h), which site hazard, wind footprint, portfolio loss, rainfall and
+compound hazard share: the checks of sites and groups, the order the kernel wants (the storms of a group next to each other, the
+sites in Z-order), the call, and the way back to the caller's site and storm order."""
 import collections
 import ctypes as C
 
@@ -33,7 +33,7 @@ def spatial_order(lon, lat, xp):
 
 
 def site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, return_max, engine, device, make_args,
-              site_extras=(), more_outputs=()):
+              site_extras=(), more_outputs=(), count_cells=None):
     """Checks the sites and groups, puts the storms of a group next to each other and the sites in spatial order, runs
     ``entry + '_dev'`` (torch tensors, on the current stream) or ``entry + '_host'`` (NumPy) and returns ``counts``,
     ``thresholds`` and with return_max ``site_max`` in the caller's site and storm order.  planes, fl: of analysis.as_planes.
@@ -41,7 +41,9 @@ def site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, retu
     passed.
 
     site_extras: further [n_site] inputs (or None), which go through the site permutation with the coordinates.  more_outputs:
-    (name, axis) pairs of fp64 outputs along 'trk', 'group' or 'site', which come back under their names in the caller's order."""
+    (name, axis) pairs of fp64 outputs along 'trk', 'group' or 'site', or 'pair' for a second [n_site][n_trk] plane like
+    site_max, which come back under their names in the caller's order.  count_cells: the counts of a (site, group) when they are
+    not one per threshold (None: n_bin)."""
     xp = fl.xp
     site_lon, site_lat = (fl.conv(a).reshape(-1) for a in (site_lon, site_lat))
     if site_lon.shape[0] != site_lat.shape[0] or site_lon.shape[0] < 1:
@@ -68,9 +70,10 @@ def site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, retu
         planes = [fl.new((1, n_t), 'f8') for _ in planes]
     slon, slat = fl.contiguous(site_lon[site_order]), fl.contiguous(site_lat[site_order])
     extras = [None if a is None else fl.contiguous(a[site_order]) for a in site_extras]
-    counts = fl.new((n_site, n_groups, max(n_bin, 1)), 'i4')
+    counts = fl.new((n_site, n_groups, max(n_bin if count_cells is None else int(count_cells), 1)), 'i4')
     smax = fl.new((n_site, max(n_trk, 1)), 'f8') if return_max else None
-    more = [fl.new((max(dict(trk=n_trk, group=n_groups, site=n_site)[axis], 1),), 'f8') for _, axis in more_outputs]
+    more = [fl.new((n_site, max(n_trk, 1)) if axis == 'pair' else (max(dict(trk=n_trk, group=n_groups, site=n_site)[axis], 1),), 'f8')
+            for _, axis in more_outputs]
     ptr = lambda a: None if a is None else fl.ptr(a)                                      # noqa: E731
     args = make_args(ScanArgs(
         tracks=dict(n_trk=n_trk, n_t=n_t, row_stride=n_t, n_group=n_groups, group_off=group_off.ctypes.data_as(C.POINTER(C.c_int64))),
@@ -85,9 +88,18 @@ def site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, retu
         out = xp.empty_like(a)
         out[site_order] = a
         return out
+    def by_pair(a):
+        out = by_site(a[:, :n_trk])
+        if not sorted_:
+            un = xp.empty_like(out)
+            un[:, idx] = out
+            out = un
+        return out
     res = dict(counts=by_site(counts), thresholds=thr)
     for (name, axis), a in zip(more_outputs, more):
-        if axis == 'group':
+        if axis == 'pair':
+            res[name] = by_pair(a)
+        elif axis == 'group':
             res[name] = a[:n_groups]
         elif axis == 'site':
             res[name] = by_site(a)
@@ -95,10 +107,5 @@ def site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, retu
             res[name] = xp.empty_like(a[:n_trk])
             res[name][idx] = a[:n_trk]
     if return_max:
-        out = by_site(smax[:, :n_trk])
-        if not sorted_:
-            un = xp.empty_like(out)
-            un[:, idx] = out
-            out = un
-        res['site_max'] = out
+        res['site_max'] = by_pair(smax)
     return res
