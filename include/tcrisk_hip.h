@@ -777,6 +777,30 @@ int tcr_compound_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const double 
 /* (site, record) pairs the last tcr_compound_* call of this context evaluated after culling with the larger radius; waits for it */
 int tcr_compound_pairs(tcr_ctx *ctx, int64_t *pairs);
 
+/* ---- row selection (return levels): the k-th largest value of every row of a per-storm plane ----------------------------- */
+/* replaces: nothing in the reference's code; the inverse of the return periods above.  With return_period = total_years /
+ * count(peak >= v), the level of period T at a site is the k-th largest storm peak there, k the smallest integer with
+ * k T >= total_years: an order statistic of the site's row of site_max / site_value, taken while the plane is on the device.
+ *   plane           [n_row][row_stride] fp64, of which the first n_col values of a row are the row; NaN is "absent".
+ *   order           that of the key of a double: its bits, every bit flipped for a negative, the sign bit flipped otherwise, as an
+ *                   unsigned integer: -inf < negatives < -0.0 < +0.0 < positives < +inf.  A NaN of either sign has no place in it.
+ *   level           [n_row][n_rank]: level[r][j] is the ranks[j]-th largest value of row r that is not NaN, one of the row's own
+ *                   values bit for bit (no arithmetic touches a value); NaN when the row holds fewer such values.
+ *   n_valid         [n_row] (int32, optional, NULL: not written): how many values of the row are not NaN.
+ * Arguments: n_row >= 0, 1 <= n_col <= 2^31 - 1, row_stride >= n_col, 1 <= n_rank <= TCR_SELECT_MAX_RANKS, ranks >= 1 in any order,
+ * repeats allowed.  Every message begins with "tcr_select:" and nothing is launched after one.
+ * One workgroup per row compacts the keys of the row's non-NaN values into LDS in one pass; a row with at most
+ * TCR_SELECT_LDS_KEYS of them is selected there, a longer one from the row in global memory, by the same radix selection (8-bit
+ * digits from the top, all ranks together).  The result is a function of the row's multiset of values alone: bit-identical from
+ * run to run, on both paths, and whatever the order of the values.  _dev: plane, level and n_valid are device memory,
+ * asynchronous on `stream`; ranks is host memory in both entry points.  No workspace: calls on one context need no ordering. */
+#define TCR_SELECT_LDS_KEYS 8192      /* keys a row may hold in LDS; rows with more take the global path */
+#define TCR_SELECT_MAX_RANKS 64
+int tcr_select_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, int32_t n_rank,
+                   const int64_t *ranks, double *level, int32_t *n_valid, void *stream);
+int tcr_select_host(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, int32_t n_rank,
+                    const int64_t *ranks, double *level, int32_t *n_valid);
+
 #ifdef __cplusplus
 }
 #endif

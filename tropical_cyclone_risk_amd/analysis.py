@@ -214,6 +214,16 @@ def parse_grid(text):
     return parse_range(parts[0], '--grid lon'), parse_range(parts[1], '--grid lat')
 
 
+def parse_periods(text):
+    try:
+        T = [float(x) for x in text.split(',')]
+    except ValueError:
+        raise argparse.ArgumentTypeError('--return-periods: expected T1,T2,..., got %r' % text)
+    if not T or not all(np.isfinite(t) and t > 0 for t in T):
+        raise argparse.ArgumentTypeError('--return-periods: need finite values > 0, got %r' % text)
+    return np.array(T)
+
+
 def add_track_args(p, out_default):
     p.add_argument('tracks', nargs='+', help='track files (ensemble members); every year of every file is one group')
     p.add_argument('--out', default=out_default)
@@ -236,6 +246,12 @@ def add_footprint_args(p):
 
 def add_threshold_arg(p):
     p.add_argument('--thresholds', type=lambda t: parse_range(t, '--thresholds'), default=DEFAULT_THRESHOLDS, metavar='LO:HI:STEP')
+
+
+def add_return_period_arg(p, what):
+    p.add_argument('--return-periods', type=parse_periods, default=None, metavar='T1,T2,...',
+                   help='also write return_level, the %s of these return periods (years) at every site, and n_reach '
+                        '(levels.site_return_levels)' % what)
 
 
 def read_sites_csv(fn):

@@ -10,6 +10,8 @@ The analysis of the reference's ``notebooks/sample_analysis.ipynb``, for many si
 3. the return period ``total_years / exceedance_count`` (``inf`` where the count is 0).
 
     python -m tropical_cyclone_risk_amd.hazard TRACKS.nc [TRACKS_e0.nc ...] --site=-80.1918,25.7617 --out hazard.npz
+
+With ``--return-periods 10,50,100`` also the inverse, the near-site intensity of those return periods at every site (levels.py).
 """
 import argparse
 import ctypes as C
@@ -78,6 +80,7 @@ def parse_args(argv=None):
     analysis.add_site_args(p)
     p.add_argument('--radius-km', type=float, default=100.0)
     analysis.add_threshold_arg(p)
+    analysis.add_return_period_arg(p, 'near-site intensity (m/s)')
     analysis.add_track_args(p, 'hazard.npz')
     a = p.parse_args(argv)
     if not (a.site or a.sites or a.grid):
@@ -92,14 +95,23 @@ def main(argv=None):
         raise SystemExit('no sites')
     lon, lat, vmax, groups, gfile, gyear = load_groups(args.tracks)
     total_years = len(gfile)
-    res = site_hazard(lon, lat, vmax, groups, site_lon, site_lat, radius_km=args.radius_km, thresholds=args.thresholds,
-                      device=args.device, n_groups=total_years)
+    kw = dict(radius_km=args.radius_km, thresholds=args.thresholds, n_groups=total_years)
+    more = {}
+    if args.return_periods is None:
+        res = site_hazard(lon, lat, vmax, groups, site_lon, site_lat, device=args.device, **kw)
+    else:
+        from . import levels
+        res = levels.device_levels(lambda t, x, y: site_hazard(t[0], t[1], t[2], groups, x, y, return_max=True, **kw),
+                                   (lon, lat, vmax), site_lon, site_lat, total_years, args.return_periods, 'site_max', args.device)
+        more = levels.npz_keys(res)
     rp = return_periods(res['counts'], total_years)
     np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,
-             total_years=total_years, radius_km=args.radius_km, **analysis.group_meta(args.tracks, gfile, gyear))
+             total_years=total_years, radius_km=args.radius_km, **analysis.group_meta(args.tracks, gfile, gyear), **more)
     print('%d sites, %d storms, %d groups (%d files), total_years = %d -> %s'
           % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.out))
     analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp)
+    if more:
+        levels.print_return_levels(res, site_lon, site_lat)
     return 0
 
 

@@ -29,10 +29,10 @@ import numpy as np
 
 from . import _lib, analysis, windfield
 from .analysis import DEFAULT_THRESHOLDS, to_numpy
+from .levels import DEFAULT_RETURN_PERIODS, ranks_of_periods
 from .sitescan import site_scan
 
 V_THRESH, V_HALF = 25.7, 74.7          # m/s: CLIMADA's defaults of the Emanuel (2011) function
-DEFAULT_RETURN_PERIODS = (10.0, 25.0, 50.0, 100.0, 250.0)
 
 
 def damage(m, v_thresh=V_THRESH, v_half=V_HALF):
@@ -114,15 +114,10 @@ def loss_curve(year_losses, total_years, return_periods=DEFAULT_RETURN_PERIODS):
     total_years = int(total_years)
     if total_years < 1 or y.size > total_years:
         raise ValueError('total_years must be >= 1 and >= the number of year losses')
-    T = np.asarray(return_periods, dtype=np.float64).reshape(-1)
-    if not (np.isfinite(T).all() and (T > 0).all()):
-        raise ValueError('return periods must be finite and > 0')
+    k, defined = ranks_of_periods(return_periods, total_years)
     desc = np.zeros(total_years)
     desc[:y.size] = np.sort(y)[::-1]
-    k = np.ceil(total_years / T).astype(np.int64)
-    k += (k * T < total_years)                          # the rounding of the division must not make k too small ...
-    k -= ((k - 1) * T >= total_years) & (k > 1)         # ... or too large
-    return np.where(T > total_years, np.nan, desc[np.clip(k, 1, total_years) - 1])
+    return np.where(defined, desc[np.clip(k, 1, total_years) - 1], np.nan)
 
 
 def average_annual_loss(year_agg, total_years):
@@ -132,16 +127,6 @@ def average_annual_loss(year_agg, total_years):
 
 
 # ---------------------------------------------------------------------------------------------------------------- CLI
-def _periods(text):
-    try:
-        T = [float(x) for x in text.split(',')]
-    except ValueError:
-        raise argparse.ArgumentTypeError('--return-periods: expected T1,T2,..., got %r' % text)
-    if not T or not all(np.isfinite(t) and t > 0 for t in T):
-        raise argparse.ArgumentTypeError('--return-periods: need finite values > 0, got %r' % text)
-    return np.array(T)
-
-
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog='python -m tropical_cyclone_risk_amd.loss',
                                 description='Event, year and site losses and AEP / OEP loss curves of track files for an exposure.')
@@ -150,7 +135,7 @@ def parse_args(argv=None):
     p.add_argument('--v-thresh', type=float, default=V_THRESH, help='wind below which nothing is damaged (m/s)')
     p.add_argument('--v-half', type=float, default=V_HALF, help='wind of half damage (m/s) where the exposure gives none')
     analysis.add_footprint_args(p)
-    p.add_argument('--return-periods', type=_periods, default=np.array(DEFAULT_RETURN_PERIODS), metavar='T1,T2,...')
+    p.add_argument('--return-periods', type=analysis.parse_periods, default=np.array(DEFAULT_RETURN_PERIODS), metavar='T1,T2,...')
     analysis.add_track_args(p, 'loss.npz')
     return p.parse_args(argv)
 

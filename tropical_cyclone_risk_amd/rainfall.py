@@ -15,6 +15,8 @@ The contract is the header's "rainfall footprint" section (include/tcrisk_hip.h)
 topography, and decay after landfall.
 
     python -m tropical_cyclone_risk_amd.rainfall TRACKS.nc [TRACKS_e0.nc ...] --site=-80.1918,25.7617 --out rain.npz
+
+With ``--return-periods 10,50,100`` also the inverse, the rain of those return periods at every site (levels.py).
 """
 import argparse
 import ctypes as C
@@ -113,6 +115,7 @@ def parse_args(argv=None):
     p.add_argument('--substeps', type=int, default=1, help='evaluation points per sample interval (1 = the samples only)')
     p.add_argument('--thresholds', type=lambda t: analysis.parse_range(t, '--thresholds'), default=None, metavar='LO:HI:STEP',
                    help='mm (total) or mm/h (peak-rate); default for total: %s' % ' '.join('%g' % t for t in DEFAULT_RAIN_THRESHOLDS))
+    analysis.add_return_period_arg(p, 'storm-total rain (mm) or peak rain rate (mm/h)')
     analysis.add_track_args(p, 'rain.npz')
     a = p.parse_args(argv)
     if not (a.site or a.sites or a.grid):
@@ -132,15 +135,26 @@ def main(argv=None):
     lon, lat, vmax, groups, gfile, gyear, more = analysis.load_groups(args.tracks, extra=('time',))
     dt = analysis.sample_spacing(more['time'])
     total_years = len(gfile)
-    res = site_rain(lon, lat, vmax, groups, site_lon, site_lat, dt, stat=args.stat, r_out_km=args.r_out_km, substeps=args.substeps,
-                    thresholds=args.thresholds, device=args.device, n_groups=total_years)
+    kw = dict(stat=args.stat, r_out_km=args.r_out_km, substeps=args.substeps, thresholds=args.thresholds, n_groups=total_years)
+    more = {}
+    if args.return_periods is None:
+        res = site_rain(lon, lat, vmax, groups, site_lon, site_lat, dt, device=args.device, **kw)
+    else:
+        from . import levels
+        res = levels.device_levels(lambda t, x, y: site_rain(t[0], t[1], t[2], groups, x, y, dt, return_values=True, **kw),
+                                   (lon, lat, vmax), site_lon, site_lat, total_years, args.return_periods, STATS[args.stat][1],
+                                   args.device)
+        more = levels.npz_keys(res)
     rp = hazard.return_periods(res['counts'], total_years)
     np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,
              total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps, stat=args.stat, dt_s=dt,
-             **analysis.group_meta(args.tracks, gfile, gyear))
+             **analysis.group_meta(args.tracks, gfile, gyear), **more)
     print('%d sites, %d storms, %d groups (%d files), total_years = %d, %s, r_out = %g km, %d substeps -> %s'
           % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.stat, args.r_out_km, args.substeps, args.out))
-    analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp, unit='mm' if args.stat == 'total' else 'mm/h')
+    unit = 'mm' if args.stat == 'total' else 'mm/h'
+    analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp, unit=unit)
+    if more:
+        levels.print_return_levels(res, site_lon, site_lat, unit=unit)
     return 0
 
 

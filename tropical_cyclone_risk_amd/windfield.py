@@ -14,6 +14,8 @@ footprint is the pipeline's ``vmax_trks``.  On the GPU (``csrc/tcr_windfield.hip
 The contract is the header's "wind footprint" section (include/tcrisk_hip.h).
 
     python -m tropical_cyclone_risk_amd.windfield TRACKS.nc [TRACKS_e0.nc ...] --site=-80.1918,25.7617 --out wind.npz
+
+With ``--return-periods 10,50,100`` also the inverse, the peak wind of those return periods at every site (levels.py).
 """
 import argparse
 import ctypes as C
@@ -127,6 +129,7 @@ def parse_args(argv=None):
     analysis.add_site_args(p)
     analysis.add_footprint_args(p)
     analysis.add_threshold_arg(p)
+    analysis.add_return_period_arg(p, 'peak wind (m/s)')
     analysis.add_track_args(p, 'wind.npz')
     a = p.parse_args(argv)
     if not (a.site or a.sites or a.grid):
@@ -141,17 +144,26 @@ def main(argv=None):
         raise SystemExit('no sites')
     lon, lat, _, v, env, groups, gfile, gyear, dt = analysis.load_wind_planes(args.tracks)
     total_years = len(gfile)
-    res = site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt, rmax_km=args.rmax_km, ck_cd=args.ck_cd,
-                    r_out_km=args.r_out_km, substeps=args.substeps, thresholds=args.thresholds, device=args.device,
-                    n_groups=total_years)
+    kw = dict(rmax_km=args.rmax_km, ck_cd=args.ck_cd, r_out_km=args.r_out_km, substeps=args.substeps, thresholds=args.thresholds,
+              n_groups=total_years)
+    more = {}
+    if args.return_periods is None:
+        res = site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt, device=args.device, **kw)
+    else:
+        from . import levels
+        res = levels.device_levels(lambda t, x, y: site_wind(t[0], t[1], t[2], t[3], groups, x, y, dt, return_max=True, **kw),
+                                   (lon, lat, v, tuple(env)), site_lon, site_lat, total_years, args.return_periods, 'site_max', args.device)
+        more = levels.npz_keys(res)
     rp = hazard.return_periods(res['counts'], total_years)
     np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,
              total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps,
              rmax_km=np.nan if args.rmax_km is None else args.rmax_km, dt_s=dt,
-             **analysis.group_meta(args.tracks, gfile, gyear))
+             **analysis.group_meta(args.tracks, gfile, gyear), **more)
     print('%d sites, %d storms, %d groups (%d files), total_years = %d, r_out = %g km, %d substeps -> %s'
           % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.r_out_km, args.substeps, args.out))
     analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp)
+    if more:
+        levels.print_return_levels(res, site_lon, site_lat)
     return 0
 
 
