@@ -801,6 +801,50 @@ int tcr_select_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_c
 int tcr_select_host(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, int32_t n_rank,
                     const int64_t *ranks, double *level, int32_t *n_valid);
 
+/* ---- row tail fit (return levels past the record): a generalized Pareto tail on the k largest values of every row ---------- */
+/* replaces: nothing in the reference's code.  Row selection stops at T = total_years, and its last order statistics are single
+ * storms; this is the standard peaks-over-threshold step on the same plane: per row, a generalized Pareto distribution (GPD)
+ * fitted to the excesses of the k largest values over the (k+1)-th, and the level of any return period read off the fit.
+ * For one row of a [n_row][n_col] fp64 plane, with k exceedances (2 <= k <= TCR_TAIL_MAX_K = 2048), total_years > 0 and return
+ * periods T_j (1 to 64 of them, finite, > 0):
+ *   1. n_valid is the number of values that are not NaN, in tcr_select's key order.  If n_valid < k + 1, the fit is undefined.
+ *   2. u is the (k+1)-th largest value, bit for bit one of the row's own.  The sample is the k largest values.  Ties at u are
+ *      included until there are k; they have excess +0.0.
+ *   3. Excesses are y_1 <= ... <= y_k, with y_i = x_i - u taken after sorting ascending.
+ *   4. Two sums are formed with a fixed tree.  Pad to P with +0.0, where P is the next power of two >= k.  Then repeat
+ *      s[i] = s[2i] + s[2i+1] until one value is left.
+ *        S0 = tree(y_i)
+ *        S1 = tree((double)(k - i) * y_i), with i 1-based
+ *        a0 = S0 / k
+ *        a1 = S1 / ((double)k * (double)(k - 1))
+ *   5. d = a0 - 2.0 * a1.  The fit is defined iff d > 0 and a1 > 0.  An Inf or NaN among the excesses fails this by itself.
+ *      These are the Hosking & Wallis (1987) probability-weighted-moment (PWM) estimators:
+ *        xi = 2.0 - a0 / d
+ *        sigma = 2.0 * a0 * a1 / d, evaluated as ((2.0 * a0) * a1) / d
+ *   6. L_j = log((k / total_years) * T_j) is computed once on the host in fp64.  The level is NaN when L_j < 0, because T is then
+ *      shorter than the threshold's own return period and return_level is the answer there.  Otherwise:
+ *        level_j = u + sigma * L_j when xi == 0
+ *        level_j = u + sigma * expm1(xi * L_j) / xi otherwise
+ *   7. Undefined fit: xi, sigma and all levels are NaN.  u is still reported when n_valid >= k + 1, NaN otherwise.  n_valid is
+ *      always reported.
+ * Nothing is clamped.  xi <= 1 follows from 2 a1 <= a0 for ascending non-negative excesses.
+ * The translation unit is built with -ffp-contract=off.  Steps 1 to 5 are IEEE adds, multiplies, divides and exact int
+ * conversions in a stated order, so u, xi and sigma are a function of the row's multiset of values alone, bit for bit; only step
+ * 6 goes through log and expm1.
+ *   plane, n_row, n_col, row_stride: as tcr_select_*.      periods   [n_period] fp64, host memory in both entry points.
+ *   param           [n_row][3]: u, xi, sigma.              level     [n_row][n_period].
+ *   n_valid         [n_row] (int32, optional, NULL: not written).
+ * Arguments: tcr_select's rules for the plane; 2 <= k <= TCR_TAIL_MAX_K, total_years finite and > 0,
+ * 1 <= n_period <= TCR_SELECT_MAX_RANKS, periods finite and > 0.  Every message begins with "tcr_tail:" and nothing is launched
+ * after one.  n_row == 0 returns 0.  One workgroup per row: tcr_select's compaction and its selection of rank k + 1 (from LDS or
+ * from the row, as there), a gather of the values above u, a bitonic sort in LDS, the sums and the levels.  _dev: plane, param,
+ * level and n_valid are device memory, asynchronous on `stream`.  No workspace: calls on one context need no ordering. */
+#define TCR_TAIL_MAX_K 2048
+int tcr_tail_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, int32_t k, double total_years,
+                 int32_t n_period, const double *periods, double *param, double *level, int32_t *n_valid, void *stream);
+int tcr_tail_host(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, int32_t k, double total_years,
+                  int32_t n_period, const double *periods, double *param, double *level, int32_t *n_valid);
+
 #ifdef __cplusplus
 }
 #endif

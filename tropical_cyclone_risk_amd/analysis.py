@@ -224,6 +224,16 @@ def parse_periods(text):
     return np.array(T)
 
 
+def parse_exceedances(text):
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--tail-exceedances: expected an integer, got %r' % text)
+    if not 2 <= k <= _lib.TAIL_MAX_K:
+        raise argparse.ArgumentTypeError('--tail-exceedances: need 2 <= K <= %d, got %r' % (_lib.TAIL_MAX_K, text))
+    return k
+
+
 def add_track_args(p, out_default):
     p.add_argument('tracks', nargs='+', help='track files (ensemble members); every year of every file is one group')
     p.add_argument('--out', default=out_default)
@@ -252,6 +262,16 @@ def add_return_period_arg(p, what):
     p.add_argument('--return-periods', type=parse_periods, default=None, metavar='T1,T2,...',
                    help='also write return_level, the %s of these return periods (years) at every site, and n_reach '
                         '(levels.site_return_levels)' % what)
+    p.add_argument('--tail-exceedances', type=parse_exceedances, default=None, metavar='K',
+                   help='with --return-periods: also write tail_level, the levels from a generalized Pareto tail fitted to the K '
+                        'largest storms of every site (levels.row_tail: return periods past the record), tail_xi, tail_sigma and '
+                        'tail_threshold')
+
+
+def check_return_period_args(p, a):
+    """What the options of add_return_period_arg ask of each other, after parsing."""
+    if a.tail_exceedances is not None and a.return_periods is None:
+        p.error('--tail-exceedances needs --return-periods')
 
 
 def read_sites_csv(fn):

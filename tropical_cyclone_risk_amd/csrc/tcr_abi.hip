@@ -2351,3 +2351,4 @@ int tcr_round_graph_stats(tcr_ctx *ctx, int64_t *n_graphs, int64_t *n_replays)
 #include "tcr_rainfall.hip"              // rainfall footprint (R-CLIPER rain rate integrated along the track, or its peak, at sites)
 #include "tcr_compound.hip"              // compound wind-rain hazard (both footprints in one scan, joint exceedance counts)
 #include "tcr_select.hip"                // row selection (the k-th largest of every row of a per-storm plane: return levels)
+#include "tcr_tail.hip"                  // row tail fit (a GPD fitted to the k largest of every row: return levels past the record)

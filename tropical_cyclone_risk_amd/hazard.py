@@ -11,7 +11,8 @@ The analysis of the reference's ``notebooks/sample_analysis.ipynb``, for many si
 
     python -m tropical_cyclone_risk_amd.hazard TRACKS.nc [TRACKS_e0.nc ...] --site=-80.1918,25.7617 --out hazard.npz
 
-With ``--return-periods 10,50,100`` also the inverse, the near-site intensity of those return periods at every site (levels.py).
+With ``--return-periods 10,50,100`` also the inverse, the near-site intensity of those return periods at every site (levels.py);
+with ``--tail-exceedances K`` on top, also their levels from a tail fitted to the site's K largest storms (``levels.row_tail``).
 """
 import argparse
 import ctypes as C
@@ -83,6 +84,7 @@ def parse_args(argv=None):
     analysis.add_return_period_arg(p, 'near-site intensity (m/s)')
     analysis.add_track_args(p, 'hazard.npz')
     a = p.parse_args(argv)
+    analysis.check_return_period_args(p, a)
     if not (a.site or a.sites or a.grid):
         p.error('give sites with --site, --sites or --grid')
     return a
@@ -102,7 +104,8 @@ def main(argv=None):
     else:
         from . import levels
         res = levels.device_levels(lambda t, x, y: site_hazard(t[0], t[1], t[2], groups, x, y, return_max=True, **kw),
-                                   (lon, lat, vmax), site_lon, site_lat, total_years, args.return_periods, 'site_max', args.device)
+                                   (lon, lat, vmax), site_lon, site_lat, total_years, args.return_periods, 'site_max', args.device,
+                                   tail_exceedances=args.tail_exceedances)
         more = levels.npz_keys(res)
     rp = return_periods(res['counts'], total_years)
     np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,

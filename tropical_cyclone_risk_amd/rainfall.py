@@ -16,7 +16,8 @@ topography, and decay after landfall.
 
     python -m tropical_cyclone_risk_amd.rainfall TRACKS.nc [TRACKS_e0.nc ...] --site=-80.1918,25.7617 --out rain.npz
 
-With ``--return-periods 10,50,100`` also the inverse, the rain of those return periods at every site (levels.py).
+With ``--return-periods 10,50,100`` also the inverse, the rain of those return periods at every site (levels.py); with
+``--tail-exceedances K`` on top, also their levels from a tail fitted to the site's K largest storms (``levels.row_tail``).
 """
 import argparse
 import ctypes as C
@@ -118,6 +119,7 @@ def parse_args(argv=None):
     analysis.add_return_period_arg(p, 'storm-total rain (mm) or peak rain rate (mm/h)')
     analysis.add_track_args(p, 'rain.npz')
     a = p.parse_args(argv)
+    analysis.check_return_period_args(p, a)
     if not (a.site or a.sites or a.grid):
         p.error('give sites with --site, --sites or --grid')
     if a.thresholds is None:
@@ -143,7 +145,7 @@ def main(argv=None):
         from . import levels
         res = levels.device_levels(lambda t, x, y: site_rain(t[0], t[1], t[2], groups, x, y, dt, return_values=True, **kw),
                                    (lon, lat, vmax), site_lon, site_lat, total_years, args.return_periods, STATS[args.stat][1],
-                                   args.device)
+                                   args.device, tail_exceedances=args.tail_exceedances)
         more = levels.npz_keys(res)
     rp = hazard.return_periods(res['counts'], total_years)
     np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,

@@ -15,7 +15,9 @@ The contract is the header's "wind footprint" section (include/tcrisk_hip.h).
 
     python -m tropical_cyclone_risk_amd.windfield TRACKS.nc [TRACKS_e0.nc ...] --site=-80.1918,25.7617 --out wind.npz
 
-With ``--return-periods 10,50,100`` also the inverse, the peak wind of those return periods at every site (levels.py).
+With ``--return-periods 10,50,100`` also the inverse, the peak wind of those return periods at every site (levels.py); with
+``--tail-exceedances K`` on top, also their levels from a generalized Pareto tail fitted to the site's K largest storms, which
+reach past the record (``levels.row_tail``).
 """
 import argparse
 import ctypes as C
@@ -132,6 +134,7 @@ def parse_args(argv=None):
     analysis.add_return_period_arg(p, 'peak wind (m/s)')
     analysis.add_track_args(p, 'wind.npz')
     a = p.parse_args(argv)
+    analysis.check_return_period_args(p, a)
     if not (a.site or a.sites or a.grid):
         p.error('give sites with --site, --sites or --grid')
     return a
@@ -152,7 +155,8 @@ def main(argv=None):
     else:
         from . import levels
         res = levels.device_levels(lambda t, x, y: site_wind(t[0], t[1], t[2], t[3], groups, x, y, dt, return_max=True, **kw),
-                                   (lon, lat, v, tuple(env)), site_lon, site_lat, total_years, args.return_periods, 'site_max', args.device)
+                                   (lon, lat, v, tuple(env)), site_lon, site_lat, total_years, args.return_periods, 'site_max', args.device,
+                                   tail_exceedances=args.tail_exceedances)
         more = levels.npz_keys(res)
     rp = hazard.return_periods(res['counts'], total_years)
     np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,
