@@ -65,13 +65,18 @@ __device__ __forceinline__ int cell_of(const CellOrderArgs &a, double lo, double
 //   state[2 + t]  (generation << 32) | count of tile t — valid for this launch when the generation matches
 // The last tile writes *total and leaves ticket = 0, generation + 1 behind for the next launch on this scratch (launches
 // that share a scratch are ordered by their stream).
+// The words are read and written with RELAXED atomics: a tile word carries everything its readers use (count and generation),
+// so nothing else has to become visible with it, and what a launch leaves behind reaches the next one through the kernel
+// boundary.  An agent-scope acquire invalidates, and a release writes back, the L2 of the XCD it runs on — the cache the
+// integrator waves of the other batches live on (profiles/frontend_fused_ab.txt: with an acquire per look-back word and a
+// release per tile this kernel took 32.5 us for a 515 000-candidate round, relaxed it takes 26.9 us).
 __device__ __forceinline__ unsigned long long ld_agent(const unsigned long long *p)
 {
-    return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void st_agent(unsigned long long *p, unsigned long long v)
 {
-    __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // KEY: the selection is about to be put into locality order (tcr_round_dev): what k_cell_key would do in a launch of its own
