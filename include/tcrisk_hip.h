@@ -436,7 +436,10 @@ int tcr_init_m_host(tcr_ctx *ctx, const tcr_storms *storms_host, double dvdt, do
  * fn 0: a / b without range scaling (qdiv_nz), 1: sqrt (qsqrt), 2: sqrt of a positive argument (qsqrt_pos), 3: a ** (-1/5)
  * (inv_fifth_root: err ** -0.2 of scipy/integrate/_ivp/rk.py:160), 4: a ** -0.4 (strat_pow: t_strat ** -0.4,
  * intensity/coupled_fast.py:91), 5: cos(a) for a in [-pi / 2, pi / 2] (cos_lat: np.cos(np.deg2rad(lat)), track/bam_track.py:139).
- * Host arrays; b may be NULL except for fn 0. */
+ * fn 6-12: the float instantiations the fp32 variant runs — 6: qdiv_nz<float> (a / b), 7: qsqrt<float>, 8: qsqrt_pos<float>,
+ * 9: inv_fifth_root<float> (pow(a, -0.2f)), 10: strat_pow<float> (pow(a, -0.4f)), 11: cos_lat<float>, 12: exp(-a) in float (the
+ * ocean feedback's exponential, coupled_fast.py:94); operands are rounded to float on the device, results widened to double.
+ * Host arrays; b may be NULL except for fn 0 and 6. */
 int tcr_probe_math_host(tcr_ctx *ctx, int32_t fn, int64_t n, const double *a, const double *b, double *out);
 /* replaces: Coupled_FAST.dydt (coupled_fast.py:196-207), ._env_winds
  * (bam_track.py:116-128) and ._calc_alpha (coupled_fast.py:65-94) at n points
@@ -445,6 +448,15 @@ int tcr_probe_rhs_host(tcr_ctx *ctx, int slot, double h_bl, const double *Fs, in
                        const double *t, const double *lon, const double *lat,
                        const double *v, const double *m,
                        double *dydt /*[n][4]*/, double *envw /*[n][4]*/, double *alpha /*[n]*/);
+/* (tests) the same evaluation in the arithmetic of the fp32 variant (tcr_integrate_f32_*): the float fields, knots and constants
+ * that variant stages, Fs and h_bl rounded to float on the host, lon / lat / v / m rounded to float on the device, t kept in double;
+ * results widened to double.  aux (may be NULL) is [n][24]: the lookups of that very evaluation — the 14 wind lookups (4 means,
+ * 10 packed covariances), vpot, chi, mld, strat, land, bathymetry, then the PI in use (0 over land), chi, the decision bits
+ * (bit0 `land == 1`, bit1 PI != 0, bit2 |land - 1| <= 1e-12) and one pad. */
+int tcr_probe_rhs_f32_host(tcr_ctx *ctx, int slot, double h_bl, const double *Fs, int64_t n,
+                           const double *t, const double *lon, const double *lat,
+                           const double *v, const double *m,
+                           double *dydt /*[n][4]*/, double *envw /*[n][4]*/, double *alpha /*[n]*/, double *aux /*[n][24] or NULL*/);
 /* Test instrument of Coupled_FAST._get_over_land (coupled_fast.py:35-38): tcr_integrate_host plus, per storm,
  * one byte per evaluation of dydt in call order — bit0 = `f_land.ev(lon, lat) == 1`, bit1 = the interpolated
  * PI is non-zero, bit2 = the land value is within 1e-12 of 1; 0xff = not evaluated.  dec is [n][cap] host

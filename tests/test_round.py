@@ -179,7 +179,8 @@ def test_compaction_single_launch_against_numpy(golden_env, built_lib):
     rng = np.random.default_rng(3)
     L, h = eng.L, eng.h
     count = torch.zeros(1, dtype=torch.int64, device=dev)
-    for n in (0, 1, 63, 2047, 2048, 2049, 4096, 100_003, 515_001, 7, 2048 * 3):
+    # (from 256 tiles of 2048 on, a thread of the look-back adds up more than one published word: 256 * 2048 + 1 and 600 * 2048 + 77)
+    for n in (0, 1, 63, 2047, 2048, 2049, 4096, 100_003, 515_001, 7, 2048 * 3, 256 * 2048, 256 * 2048 + 1, 600 * 2048 + 77):
         flags_h = rng.integers(0, 8, size=max(n, 1)).astype(np.int32)
         flags = torch.from_numpy(flags_h).to(dev)
         idx = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
@@ -199,11 +200,21 @@ def test_compaction_single_launch_against_numpy(golden_env, built_lib):
     flags = torch.from_numpy(flags_h).to(dev)
     outs = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3)]
     counts = torch.zeros(3, dtype=torch.int64, device=dev)
+    # ... and once, in the middle of them, the largest size (601 tiles: look-back threads with a second and a third word)
+    n_big = 600 * 2048 + 77
+    big_h = rng.integers(0, 4, size=n_big).astype(np.int32)
+    big = torch.from_numpy(big_h).to(dev)
+    big_out = torch.empty(n_big, dtype=torch.int32, device=dev)
+    big_count = torch.zeros(1, dtype=torch.int64, device=dev)
     for rep in range(40):
         for j, mask in enumerate((1, 2, 3)):
             eng._ck(L.tcr_compact_dev(h, n, flags.data_ptr(), mask, n, outs[j].data_ptr(), counts[j:].data_ptr(), None))
+        if rep == 20:
+            eng._ck(L.tcr_compact_dev(h, n_big, big.data_ptr(), 2, n_big, big_out.data_ptr(), big_count.data_ptr(), None))
     torch.cuda.synchronize()
     for j, mask in enumerate((1, 2, 3)):
         want = np.nonzero(flags_h & mask)[0]
         assert int(counts[j].item()) == len(want) and np.array_equal(outs[j][:len(want)].cpu().numpy(), want)
+    want = np.nonzero(big_h & 2)[0]
+    assert int(big_count.item()) == len(want) and np.array_equal(big_out[:len(want)].cpu().numpy(), want)
     eng.close()

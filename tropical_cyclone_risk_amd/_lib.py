@@ -42,7 +42,8 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_hazard_dev', 'tcr_hazard_host', 'tcr_hazard_pairs', 'tcr_land_upload', 'tcr_land_info', 'tcr_landfall_dev',
            'tcr_landfall_host', 'tcr_climatology_dev', 'tcr_climatology_host', 'tcr_windfield_dev', 'tcr_windfield_host',
            'tcr_windfield_pairs', 'tcr_loss_dev', 'tcr_loss_host', 'tcr_rainfall_dev', 'tcr_rainfall_host', 'tcr_rainfall_pairs',
-           'tcr_compound_dev', 'tcr_compound_host', 'tcr_compound_pairs', 'tcr_select_dev', 'tcr_select_host', 'tcr_tail_dev', 'tcr_tail_host')
+           'tcr_compound_dev', 'tcr_compound_host', 'tcr_compound_pairs', 'tcr_select_dev', 'tcr_select_host', 'tcr_tail_dev', 'tcr_tail_host',
+           'tcr_probe_rhs_f32_host')
 TCR_COMM_ID_BYTES = 128
 
 
@@ -227,6 +228,8 @@ def lib():
     L.tcr_seed_host.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int64, C.POINTER(Seeds)]
     L.tcr_probe_rhs_host.argtypes = [C.c_void_p, C.c_int, C.c_double, DP, C.c_int64,
                                      DP, DP, DP, DP, DP, DP, DP, DP]
+    L.tcr_probe_rhs_f32_host.argtypes = [C.c_void_p, C.c_int, C.c_double, DP, C.c_int64,
+                                         DP, DP, DP, DP, DP, DP, DP, DP, DP]
     L.tcr_fourier_table_host.argtypes = [C.c_void_p, C.c_int64, DP, DP]
     L.tcr_timing_enable.argtypes = [C.c_void_p, C.c_int]
     L.tcr_timing_last.argtypes = [C.c_void_p, DP]

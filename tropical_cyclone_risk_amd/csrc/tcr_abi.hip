@@ -1733,46 +1733,53 @@ int tcr_wind_stats_f32_host(tcr_ctx *ctx, int64_t n_samples, int64_t n_points, c
 int tcr_probe_math_host(tcr_ctx *ctx, int32_t fn, int64_t n, const double *a, const double *b, double *out)
 {
     if (!ctx) return -1;
-    if (fn < 0 || fn > 5 || n < 0 || (n > 0 && (!a || !out)) || (fn == 0 && n > 0 && !b)) return fail(ctx, "tcr_probe_math_host: bad argument");
+    if (fn < 0 || fn > 12 || n < 0 || (n > 0 && (!a || !out)) || ((fn == 0 || fn == 6) && n > 0 && !b)) return fail(ctx, "tcr_probe_math_host: bad argument");
     if (n == 0) return 0;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
     const double *d_a = B.put(a, n), *d_b = b ? B.put(b, n) : nullptr;
     double *d_o = B.get<double>(n);
     if (!d_a || (b && !d_b) || !d_o) return fail(ctx, "tcr_probe_math_host: device allocation failed");
-    hipLaunchKernelGGL(k_probe_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)fn, n, d_a, d_b, d_o);
+    if (fn <= 5) hipLaunchKernelGGL(k_probe_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)fn, n, d_a, d_b, d_o);
+    else hipLaunchKernelGGL(k_probe_math_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)fn, n, d_a, d_b, d_o);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, copy_sync(ctx->stream, out, d_o, sizeof(double) * n, hipMemcpyDeviceToHost));
     return 0;
 }
 
-int tcr_probe_rhs_host(tcr_ctx *ctx, int slot, double h_bl, const double *Fs, int64_t n, const double *t,
-                       const double *lon, const double *lat, const double *v, const double *m,
-                       double *dydt, double *envw, double *alpha)
+extern "C++" {
+namespace {
+// R = float: the table and h_bl are rounded on the host, as k_integrate<float> gets them ((R) of the fp64 table value, (R)hb0)
+template <typename R>
+int probe_rhs_impl(tcr_ctx *ctx, const char *who, int slot, double h_bl, const double *Fs, int64_t n, const double *t,
+                   const double *lon, const double *lat, const double *v, const double *m,
+                   double *dydt, double *envw, double *alpha, double *aux)
 {
     if (ready(ctx, false)) return -1;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (slot < 0 || (size_t)slot >= ctx->slots.size() || !ctx->slots[slot].wind)
-        return fail(ctx, "tcr_probe_rhs_host: slot not staged");
+        return fail(ctx, "%s: slot not staged", who);
     if (n <= 0) return 0;
     const size_t ns = (size_t)ctx->prm.n_steps;
-    std::vector<double> fs(ns * 4);
+    std::vector<R> fs(ns * 4);
     for (size_t i = 0; i < ns; ++i)
-        for (int k = 0; k < 4; ++k) fs[i * 4 + k] = Fs[(size_t)k * ns + i];
+        for (int k = 0; k < 4; ++k) fs[i * 4 + k] = (R)Fs[(size_t)k * ns + i];
     DevBuf B;
-    const double *d_fs = B.put(fs.data(), fs.size());
+    const R *d_fs = B.put(fs.data(), fs.size());
     const double *d_t = B.put(t, n), *d_lon = B.put(lon, n), *d_lat = B.put(lat, n), *d_v = B.put(v, n), *d_m = B.put(m, n);
     double *d_dy = B.get<double>(n * 4), *d_w = B.get<double>(n * 4), *d_al = B.get<double>(n);
-    if (!d_fs || !d_t || !d_lon || !d_lat || !d_v || !d_m || !d_dy || !d_w || !d_al)
-        return fail(ctx, "tcr_probe_rhs_host: device allocation failed");
-    const DevFields DF = dev_fields(ctx);
-    EvalK EK{};
+    double *d_aux = aux ? B.get<double>(n * 24) : nullptr;
+    if (!d_fs || !d_t || !d_lon || !d_lat || !d_v || !d_m || !d_dy || !d_w || !d_al || (aux && !d_aux))
+        return fail(ctx, "%s: device allocation failed", who);
+    if (!std::is_same<R, double>::value && ensure_f32(ctx, ctx->stream)) return -1;
+    EvalKT<R> EK{};
     bool affine = false;
-    if (eval_k_ready<double>(ctx, EK, &affine, ctx->stream)) return -1;
+    if (eval_k_ready<R>(ctx, EK, &affine, ctx->stream)) return -1;
+    const DevFields DF = dev_fields(ctx);
     const dim3 grid((unsigned)((n + 63) / 64)), block(64);
-#define PROBE_RHS(A, S) hipLaunchKernelGGL((k_probe_rhs<A, S>), grid, block, 0, ctx->stream, ctx->prm, DF, EK, slot, h_bl, \
-                                           d_fs, n, d_t, d_lon, d_lat, d_v, d_m, d_dy, d_w, d_al)
+#define PROBE_RHS(A, S) hipLaunchKernelGGL((k_probe_rhs<R, A, S>), grid, block, 0, ctx->stream, ctx->prm, DF, EK, slot, (R)h_bl, \
+                                           d_fs, n, d_t, d_lon, d_lat, d_v, d_m, d_dy, d_w, d_al, d_aux)
     const int sm = ctx->static_mode;
     if (affine && sm == kStatPack16) PROBE_RHS(true, kStatPack16);
     else if (affine && sm == kStatU8F32) PROBE_RHS(true, kStatU8F32);
@@ -1787,7 +1794,24 @@ int tcr_probe_rhs_host(tcr_ctx *ctx, int slot, double h_bl, const double *Fs, in
     HIPCHK(ctx, copy_sync(ctx->stream, dydt, d_dy, sizeof(double) * n * 4, hipMemcpyDeviceToHost));
     HIPCHK(ctx, copy_sync(ctx->stream, envw, d_w, sizeof(double) * n * 4, hipMemcpyDeviceToHost));
     HIPCHK(ctx, copy_sync(ctx->stream, alpha, d_al, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (aux) HIPCHK(ctx, copy_sync(ctx->stream, aux, d_aux, sizeof(double) * n * 24, hipMemcpyDeviceToHost));
     return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int tcr_probe_rhs_host(tcr_ctx *ctx, int slot, double h_bl, const double *Fs, int64_t n, const double *t,
+                       const double *lon, const double *lat, const double *v, const double *m,
+                       double *dydt, double *envw, double *alpha)
+{
+    return probe_rhs_impl<double>(ctx, "tcr_probe_rhs_host", slot, h_bl, Fs, n, t, lon, lat, v, m, dydt, envw, alpha, nullptr);
+}
+
+int tcr_probe_rhs_f32_host(tcr_ctx *ctx, int slot, double h_bl, const double *Fs, int64_t n, const double *t,
+                           const double *lon, const double *lat, const double *v, const double *m,
+                           double *dydt, double *envw, double *alpha, double *aux)
+{
+    return probe_rhs_impl<float>(ctx, "tcr_probe_rhs_f32_host", slot, h_bl, Fs, n, t, lon, lat, v, m, dydt, envw, alpha, aux);
 }
 
 extern "C++" {

@@ -859,9 +859,11 @@ struct StaticLookup {
 // fun(t, y) = Coupled_FAST.dydt (coupled_fast.py:196-207): _calc_steering_coefs (:183-192),
 // _step_bam_track (bam_track.py:131-144) on _env_winds (:116-128), _dvdt (:141-150) with
 // _get_current_vpot (:54-58), _calc_alpha/_calc_z (:65-94), _dmdt (:175-180).
-template <typename R, bool AFFINE, int SM>
-__device__ __forceinline__ RhsT<R> rhs_eval(const EvalKT<R> &K, const R *__restrict__ wind, const R *__restrict__ thermo,
-                                            const R *__restrict__ fs, R h_bl, double t, R lon, R lat, R v, R m)
+// AUX (the fp32 probe, tests only): the lookups of this very evaluation go to aux[24] as well — the 14 wind lookups q[], th[4] (vpot, chi,
+// mld, strat), lb[2] (land, bathymetry), then r.vpot, r.chi, r.dec and one pad; compiled out otherwise.
+template <typename R, bool AFFINE, int SM, bool AUX>
+__device__ __forceinline__ RhsT<R> rhs_eval_x(const EvalKT<R> &K, const R *__restrict__ wind, const R *__restrict__ thermo,
+                                              const R *__restrict__ fs, R h_bl, double t, R lon, R lat, R v, R m, R *aux)
 {
     typedef Widths<R> Wd;
     // ---- address generation: pure ALU on affine grids
@@ -887,7 +889,20 @@ __device__ __forceinline__ RhsT<R> rhs_eval(const EvalKT<R> &K, const R *__restr
     blend<R, 4, Wd::T>(CT, tx, ty, th);
     SL.finish(lb);
     rhs_tail<R>(K, h_bl, lat, v, m, th, lb, r);
+    if (AUX) {
+        for (int k = 0; k < 14; ++k) aux[k] = q[k];
+        for (int k = 0; k < 4; ++k) aux[14 + k] = th[k];
+        aux[18] = lb[0]; aux[19] = lb[1];
+        aux[20] = r.vpot; aux[21] = r.chi; aux[22] = (R)r.dec; aux[23] = R(0.0);
+    }
     return r;
+}
+
+template <typename R, bool AFFINE, int SM>
+__device__ __forceinline__ RhsT<R> rhs_eval(const EvalKT<R> &K, const R *__restrict__ wind, const R *__restrict__ thermo,
+                                            const R *__restrict__ fs, R h_bl, double t, R lon, R lat, R v, R m)
+{
+    return rhs_eval_x<R, AFFINE, SM, false>(K, wind, thermo, fs, h_bl, t, lon, lat, v, m, nullptr);
 }
 
 // Per-lane corner cache for the sequential integrator.  Consecutive RK stage points of a storm

@@ -1521,23 +1521,32 @@ __global__ __launch_bounds__(64) void k_init_m(tcr_params P, DevFields D, EvalK 
     m_out[i] = np_max(np_min(c, 1.0), 0.0);
 }
 
-template <bool AFFINE, int SM>
-__global__ __launch_bounds__(64) void k_probe_rhs(tcr_params P, DevFields D, EvalK K_host, int slot, double h_bl, const double *fs,
+// R = float (tcr_probe_rhs_f32_host): fs and h_bl arrive rounded to float as k_integrate<float> gets them, the point is rounded
+// here, t stays double; aux (may be NULL) [n][24]: the lookups of the evaluation (rhs_eval_x)
+template <typename R, bool AFFINE, int SM>
+__global__ __launch_bounds__(64) void k_probe_rhs(tcr_params P, DevFields D, EvalKT<R> K_host, int slot, R h_bl, const R *fs,
                             int64_t n, const double *t, const double *lon, const double *lat,
-                            const double *v, const double *m, double *dydt, double *envw, double *alpha)
+                            const double *v, const double *m, double *dydt, double *envw, double *alpha, double *aux)
 {
-    __shared__ EvalK K;
+    __shared__ EvalKT<R> K;
     if (threadIdx.x == 0) K = K_host;
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const DevSlot S = D.slots[slot];
-    const RhsT<double> r = rhs_eval<double, AFFINE, SM>(K, S.wind, S.thermo, fs, h_bl, t[i], lon[i], lat[i], v[i], m[i]);
-    for (int k = 0; k < 4; ++k) dydt[i * 4 + k] = r.d[k];
-    alpha[i] = r.alpha;
-    double w[4];
-    env_winds<double, AFFINE>(K, S.wind, fs, lon[i], lat[i], t[i], w);
-    for (int k = 0; k < 4; ++k) envw[i * 4 + k] = w[k];
+    RhsT<R> r;
+    if (std::is_same<R, double>::value) {
+        r = rhs_eval<R, AFFINE, SM>(K, slot_wind<R>(S), slot_thermo<R>(S), fs, h_bl, t[i], (R)lon[i], (R)lat[i], (R)v[i], (R)m[i]);
+    } else {
+        R ax[24];
+        r = rhs_eval_x<R, AFFINE, SM, true>(K, slot_wind<R>(S), slot_thermo<R>(S), fs, h_bl, t[i], (R)lon[i], (R)lat[i], (R)v[i], (R)m[i], ax);
+        if (aux) for (int k = 0; k < 24; ++k) aux[i * 24 + k] = (double)ax[k];
+    }
+    for (int k = 0; k < 4; ++k) dydt[i * 4 + k] = (double)r.d[k];
+    alpha[i] = (double)r.alpha;
+    R w[4];
+    env_winds<R, AFFINE>(K, slot_wind<R>(S), fs, (R)lon[i], (R)lat[i], t[i], w);
+    for (int k = 0; k < 4; ++k) envw[i * 4 + k] = (double)w[k];
 }
 
 // The arithmetic helpers of tcr_device.h's policy on their own (tcr_probe_math_host: tests pin their accuracy against NumPy)
@@ -1558,6 +1567,28 @@ __global__ __launch_bounds__(256) void k_probe_math(int fn, int64_t n, const dou
     default: break;
     }
     out[i] = r;
+}
+
+// fn 6-12 of tcr_probe_math_host: the float instantiations of the same helpers (plain /, sqrt, pow, cos) and the float exp(-x) of
+// rhs_intensity's alpha; operands rounded to float here, results widened
+__global__ __launch_bounds__(256) void k_probe_math_f32(int fn, int64_t n, const double *__restrict__ a, const double *__restrict__ b,
+                                                        double *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float x = (float)a[i], y = b ? (float)b[i] : 0.0f;
+    float r = 0.0f;
+    switch (fn) {
+    case 6: r = qdiv_nz<float>(x, y); break;
+    case 7: r = qsqrt<float>(x); break;
+    case 8: r = qsqrt_pos<float>(x); break;
+    case 9: r = inv_fifth_root<float>(x); break;
+    case 10: r = strat_pow<float>(x); break;
+    case 11: r = cos_lat<float>(x); break;
+    case 12: r = exp(-x); break;
+    default: break;
+    }
+    out[i] = (double)r;
 }
 
 }  // namespace tcr

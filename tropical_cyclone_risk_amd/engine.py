@@ -311,12 +311,21 @@ class TCEngine:
         self._ck(self.L.tcr_fourier_table_host(self.h, ph.shape[0], _dp(ph), _dp(Fs)))
         return Fs
 
-    def probe_rhs(self, slot, h_bl, Fs, t, lon, lat, v, m):
-        """dydt / _env_winds / _calc_alpha at points (coupled_fast.py:196-207, 65-94)."""
+    def probe_rhs(self, slot, h_bl, Fs, t, lon, lat, v, m, dtype='f64', aux=False):
+        """dydt / _env_winds / _calc_alpha at points (coupled_fast.py:196-207, 65-94).
+        dtype='f32': the same evaluation in the fp32 variant's arithmetic (tcr_probe_rhs_f32_host; results widened to float64);
+        aux=True (f32 only) adds a fourth result [n, 24]: the evaluation's lookups (14 wind, vpot, chi, mld, strat, land,
+        bathymetry), the PI in use, chi, the decision bits, one pad."""
         t, lon, lat, v, m = (_f64(x) for x in (t, lon, lat, v, m))
         Fs = _f64(Fs)
         n = t.size
+        assert dtype in ('f64', 'f32') and not (aux and dtype == 'f64')
         dydt = np.empty((n, 4)); envw = np.empty((n, 4)); alpha = np.empty(n)
+        if dtype == 'f32':
+            ax = np.empty((n, 24)) if aux else None
+            self._ck(self.L.tcr_probe_rhs_f32_host(self.h, int(slot), float(h_bl), _dp(Fs), n, _dp(t), _dp(lon), _dp(lat), _dp(v),
+                                                   _dp(m), _dp(dydt), _dp(envw), _dp(alpha), _dp(ax) if aux else None))
+            return (dydt, envw, alpha, ax) if aux else (dydt, envw, alpha)
         self._ck(self.L.tcr_probe_rhs_host(self.h, int(slot), float(h_bl), _dp(Fs), n, _dp(t), _dp(lon),
                                            _dp(lat), _dp(v), _dp(m), _dp(dydt), _dp(envw), _dp(alpha)))
         return dydt, envw, alpha
