@@ -1,5 +1,5 @@
 """NumPy restatement of the lookups of one RHS evaluation as the kernels spell them (csrc/tcr_device.h: locate_t, blend / blend4,
-StaticLookup; csrc/tcr_abi.hip: axis_of<float>, axis_is_affine, k_to_f32), in ONE floating type throughout and without fused
+StaticLookup; csrc/tcr_stage.hip: axis_of<float>, axis_is_affine, k_to_f32), in ONE floating type throughout and without fused
 operations: dtype=np.float32 is what the fp32 variant computes (tests/test_rhs_f32.py compares it bit for bit with
 tcr_probe_rhs_f32_host's aux), dtype=np.float64 is the same code in the reference's precision — used only to show, without a GPU,
 that the restatement equals the C oracle's bilinear (FITPACK's fpbisp / fpbspl with kx = ky = 1) bit for bit.

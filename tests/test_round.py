@@ -112,6 +112,47 @@ def test_round_equals_the_separate_calls_and_its_graph_replay(golden_env, built_
     eng.close()
 
 
+def test_a_captured_round_is_recaptured_when_a_workspace_grows(golden_env, built_lib):
+    """A round captured at one size, then a larger pipeline on the SAME engine grows the context's workspaces (every
+    allocation moves the epoch): the small round's graph holds stale addresses, so its next call must drop it, run directly
+    and capture again — never replay it.  Every round of the small pipeline equals the separate calls bit for bit."""
+    import torch
+    from tropical_cyclone_risk_amd import _lib
+    from tropical_cyclone_risk_amd.engine import TCEngine
+    from tropical_cyclone_risk_amd.pipeline import DevicePipeline
+    eng = TCEngine('GL', device=0).stage_env(golden_env)
+    n_cand, B, cap = 8192, 2048, 1500
+    mk = lambda n, b: DevicePipeline(eng, n, b, sort_storms=2.0, tc_rows_only=True, dtype='f64')
+    ref, one = mk(n_cand, B), mk(n_cand, B)
+    z = lambda *s, dt=torch.int64: torch.zeros(*s, dtype=dt, device=ref.dev)
+    packed_r, packed_o = z(cap, 9 * eng.n_steps + 3, dt=torch.float64), z(cap, 9 * eng.n_steps + 3, dt=torch.float64)
+    sr, so = z(_lib.N_STATS), z(_lib.N_STATS)        # (one descriptor: the graph is keyed by the buffers' addresses)
+    keys = [(2001, 0), (2003, 5 * n_cand), (2007, 10**9 + 17), (1999, 2 * n_cand)]
+    # the reference first: it sizes the workspaces for this batch, so the first graph round below captures at a settled epoch
+    want = []
+    for year, cand0 in keys:
+        sr.zero_(); packed_r.fill_(-7.0)
+        _staged_round(ref, year, cand0, n_cand, B, sr, packed_r, cap)
+        want.append(_snapshot(ref, packed_r, sr, B))
+        assert 0 < want[-1]['n_acc'] <= cap and 100 < want[-1]['n_pass']
+
+    def small(i):
+        so.zero_(); packed_o.fill_(-7.0)
+        one.round(keys[i][0], keys[i][1], n_cand, B, exact_count=True, stats=so, accepted=True, packed=packed_o, pack_cap=cap, graph=True)
+        _same(want[i], _snapshot(one, packed_o, so, B), ('small round', i))
+        return one.graph_stats()
+
+    assert small(0) == dict(graphs=1, replays=0)         # run directly, captured
+    assert small(1) == dict(graphs=1, replays=1)         # replayed
+    big = mk(24000, 6000)
+    big.round(2005, 0, 24000, 6000, exact_count=True)      # direct: the workspaces grow under the captured round
+    torch.cuda.synchronize()
+    assert int(big.n_passed.item()) > B
+    assert small(2) == dict(graphs=1, replays=1)         # the stale graph was dropped, not replayed: direct run, new capture
+    assert small(3) == dict(graphs=1, replays=2)         # the new graph replays
+    eng.close()
+
+
 def test_round_short_of_storms_and_over_capacity(golden_env, built_lib):
     """exact_count: a round with fewer passing seeds than the batch holds integrates exactly those (flags beyond are 0,
     stats[6] counts the short round); a round with MORE passing seeds than the batch holds reports the dropped ones in

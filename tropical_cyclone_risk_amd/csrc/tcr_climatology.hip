@@ -229,10 +229,8 @@ extern "C" {
 int tcr_climatology_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, const int32_t *group, int32_t n_group, const tcr_clim_grid *gr,
                         int32_t n_bin, const double *thresholds, const tcr_clim_out *o, void *stream_)
 {
-    if (!ctx) return -1;
-    if (clim_check(ctx, t, group, n_group, gr, n_bin, thresholds, o)) return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    hipStream_t st = enter(ctx, stream_);
+    if (!st || clim_check(ctx, t, group, n_group, gr, n_bin, thresholds, o)) return -1;
     const int64_t n_cell = gr->nlon * gr->nlat, n_map = (int64_t)n_group * n_cell;
     HIPCHK(ctx, hipMemsetAsync(o->track, 0, sizeof(int32_t) * n_map, st));
     HIPCHK(ctx, hipMemsetAsync(o->genesis, 0, sizeof(int32_t) * n_map, st));
@@ -259,14 +257,8 @@ int tcr_climatology_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, const int32_t 
         const int64_t waves = std::max<int64_t>(1, std::min<int64_t>(blocks * kClWaves, (int64_t)(kClWsBytes / (sizeof(uint64_t) * P))));
         blocks = (waves + kClWaves - 1) / kClWaves;
         const size_t bytes = sizeof(uint64_t) * (size_t)P * (size_t)std::min<int64_t>(t->n_trk, blocks * kClWaves);   // waves with a storm
-        if (ctx->cl_cap < bytes) {
-            (void)hipFree(ctx->d_cl);
-            ctx->d_cl = nullptr; ctx->cl_cap = 0;
-            uint64_t *p = nullptr;
-            if (dev_alloc(ctx, &p, bytes / sizeof(uint64_t))) return -1;
-            ctx->d_cl = p; ctx->cl_cap = bytes;
-        }
-        a.ws = static_cast<uint64_t *>(ctx->d_cl);
+        if (ctx->an.d_cl.grow(ctx, bytes / sizeof(uint64_t)) < 0) return -1;
+        a.ws = ctx->an.d_cl.p;
         a.ws_len = P;
         hipLaunchKernelGGL(k_climatology<false>, dim3((unsigned)blocks), dim3(64 * kClWaves), 0, st, a);
     }
@@ -282,9 +274,7 @@ int tcr_climatology_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, const int32_t 
 int tcr_climatology_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, const int32_t *group, int32_t n_group, const tcr_clim_grid *gr,
                          int32_t n_bin, const double *thresholds, const tcr_clim_out *o)
 {
-    if (!ctx) return -1;
-    if (clim_check(ctx, t, group, n_group, gr, n_bin, thresholds, o)) return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!enter(ctx) || clim_check(ctx, t, group, n_group, gr, n_bin, thresholds, o)) return -1;
     DevBuf B;
     const size_t n_trk = (size_t)t->n_trk;
     const size_t n_map = (size_t)n_group * (size_t)(gr->nlon * gr->nlat), n_ex = n_map * (size_t)n_bin;

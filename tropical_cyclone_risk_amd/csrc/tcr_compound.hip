@@ -135,17 +135,15 @@ int tcr_compound_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const double *vmax,
                      int64_t n_site, const double *site_lon, const double *site_lat, int32_t n_wbin, const double *wthr, int32_t n_rbin,
                      const double *rthr, int32_t *counts, double *site_wind, double *site_rain, void *stream_)
 {
-    if (!ctx) return -1;
-    if (compound_check(ctx, t, vmax, wp, rp, n_site, site_lon, site_lat, n_wbin, wthr, n_rbin, rthr, counts)) return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    hipStream_t st = enter(ctx, stream_);
+    if (!st || compound_check(ctx, t, vmax, wp, rp, n_site, site_lon, site_lat, n_wbin, wthr, n_rbin, rthr, counts)) return -1;
     const int64_t n_rec = (t->n_t - 1) * wp->substeps + 1;
     const size_t n_stage = (size_t)std::max<int64_t>(1, t->n_trk * t->n_t);
     double thr[kHzMaxBin] = {};                         // the wind list, then the rain list (n_wbin + n_rbin <= 32)
     for (int b = 0; b < n_wbin; ++b) thr[b] = wthr[b];
     for (int b = 0; b < n_rbin; ++b) thr[n_wbin + b] = rthr[b];
     const tcr_hazard_tracks ht = compound_rain_tracks(t, vmax);
-    return scan_run<CpRec>(ctx, ctx->cp, "tcr_compound", t, n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat,
+    return scan_run<CpRec>(ctx, ctx->an.cp, "tcr_compound", t, n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat,
                            std::max(wp->r_out_km, rp->r_out_km), kWfEarthR / 1000.0, (n_wbin + 1) * (n_rbin + 1), thr, counts, site_wind,
                            st, [&](const ScanArgs<CpRec> &m, void *stage, dim3 grid, size_t) {
         const size_t lds = sizeof(kJointHist) * 64 * (m.n_bin + 1);      // (the scan zeroes n_bin + 1 rows)
@@ -168,10 +166,8 @@ int tcr_compound_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const double *vmax
                       int64_t n_site, const double *site_lon, const double *site_lat, int32_t n_wbin, const double *wthr, int32_t n_rbin,
                       const double *rthr, int32_t *counts, double *site_wind, double *site_rain)
 {
-    if (!ctx) return -1;
-    if (compound_check(ctx, t, vmax, wp, rp, n_site, site_lon, site_lat, n_wbin, wthr, n_rbin, rthr, counts)) return -1;
+    if (!enter(ctx) || compound_check(ctx, t, vmax, wp, rp, n_site, site_lon, site_lat, n_wbin, wthr, n_rbin, rthr, counts)) return -1;
     if (!wind_rmax_ok(t)) return fail(ctx, "tcr_compound_host: rmax_km must be finite and > 0 at every sample of a track");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
     tcr_wind_tracks d;
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, (n_wbin + 1) * (n_rbin + 1), site_wind != nullptr);
@@ -187,6 +183,6 @@ int tcr_compound_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const double *vmax
     return scan_download(ctx, io, counts, site_wind);
 }
 
-int tcr_compound_pairs(tcr_ctx *ctx, int64_t *pairs) { return ctx ? scan_pairs(ctx, ctx->cp, "tcr_compound", pairs) : -1; }
+int tcr_compound_pairs(tcr_ctx *ctx, int64_t *pairs) { return ctx ? scan_pairs(ctx, ctx->an.cp, "tcr_compound", pairs) : -1; }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 //   TCR_DUMMY_LAUNCHES=k  k empty kernels per round, TCR_DUMMY_MODE=0..3 their shape; TCR_DUMMY_SPIN_US=t one wave spinning for
 //                         t microseconds per round (what a dispatch costs under load, section 9, round 4, item 2)
 //   TCR_GRAPH_DOT=file    dump a captured round as Graphviz
-// This header and the #ifdef TCR_EXPERIMENTS hooks of tcr_abi.hip are the only experiment code in the sources: the kernels
+// This header and the #ifdef TCR_EXPERIMENTS hooks of tcr_integrate.hip and tcr_round.hip are the only experiment code in the sources: the kernels
 // carry no #if forks beyond the arithmetic policy and the launch-shape defaults (tests/test_abi.py holds the list).  A new
 // experiment's instrumentation goes here; the results of retired ones are in DESIGN.md section 9 and DESIGN_LOG.md.
 #pragma once

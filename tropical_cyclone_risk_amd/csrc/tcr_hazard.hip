@@ -100,11 +100,9 @@ extern "C" {
 int tcr_hazard_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, int64_t n_site, const double *site_lon, const double *site_lat,
                    double radius_km, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_max, void *stream_)
 {
-    if (!ctx) return -1;
-    if (hazard_check(ctx, t, n_site, site_lon, site_lat, radius_km, n_bin, thresholds, counts)) return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    return scan_run<HzSample>(ctx, ctx->hz, "tcr_hazard", t, t->n_t, 0, n_site, site_lon, site_lat, radius_km, kHzRe, n_bin, thresholds,
+    hipStream_t st = enter(ctx, stream_);
+    if (!st || hazard_check(ctx, t, n_site, site_lon, site_lat, radius_km, n_bin, thresholds, counts)) return -1;
+    return scan_run<HzSample>(ctx, ctx->an.hz, "tcr_hazard", t, t->n_t, 0, n_site, site_lon, site_lat, radius_km, kHzRe, n_bin, thresholds,
                               counts, site_max, st, [&](const ScanArgs<HzSample> &m, void *, dim3 grid, size_t lds) {
         HzPrepArgs p{t->lon, t->lat, t->vmax, t->n_trk, t->n_t, t->row_stride, m.rows};
         return scan_launch(k_hazard_prep, p, t->n_trk, m, grid, lds, st, HazardScan{});
@@ -114,9 +112,7 @@ int tcr_hazard_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, int64_t n_site, con
 int tcr_hazard_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, int64_t n_site, const double *site_lon, const double *site_lat,
                     double radius_km, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_max)
 {
-    if (!ctx) return -1;
-    if (hazard_check(ctx, t, n_site, site_lon, site_lat, radius_km, n_bin, thresholds, counts)) return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!enter(ctx) || hazard_check(ctx, t, n_site, site_lon, site_lat, radius_km, n_bin, thresholds, counts)) return -1;
     DevBuf B;
     tcr_hazard_tracks d;
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, n_bin, site_max != nullptr);
@@ -125,6 +121,6 @@ int tcr_hazard_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, int64_t n_site, co
     return scan_download(ctx, io, counts, site_max);
 }
 
-int tcr_hazard_pairs(tcr_ctx *ctx, int64_t *pairs) { return ctx ? scan_pairs(ctx, ctx->hz, "tcr_hazard", pairs) : -1; }
+int tcr_hazard_pairs(tcr_ctx *ctx, int64_t *pairs) { return ctx ? scan_pairs(ctx, ctx->an.hz, "tcr_hazard", pairs) : -1; }
 
 }  // extern "C"

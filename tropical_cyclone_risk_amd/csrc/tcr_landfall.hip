@@ -152,7 +152,7 @@ int landfall_check(tcr_ctx *ctx, const tcr_hazard_tracks *t, int32_t max_events,
     if (t->n_trk > 0 && (!t->lon || !t->lat || !t->vmax)) return fail(ctx, "tcr_landfall: NULL track plane");
     if (max_events < 0) return fail(ctx, "tcr_landfall: max_events must be >= 0");
     if (max_events > 0 && (!ev_k || !ev_lon || !ev_lat || !ev_v || !ev_vin)) return fail(ctx, "tcr_landfall: NULL event plane");
-    if (!ctx->lf_xy) return fail(ctx, "tcr_landfall: no land grid on this context (tcr_land_upload)");
+    if (!ctx->an.lf_xy.p) return fail(ctx, "tcr_landfall: no land grid on this context (tcr_land_upload)");
     return 0;
 }
 
@@ -181,20 +181,15 @@ int tcr_land_upload(tcr_ctx *ctx, const tcr_land_grid *grid)
     std::vector<double> xy((size_t)(nlon + nlat));
     memcpy(xy.data(), grid->lon, sizeof(double) * nlon);
     memcpy(xy.data() + nlon, grid->lat, sizeof(double) * nlat);
-    (void)hipFree(ctx->lf_xy); (void)hipFree(ctx->lf_bits);
-    ctx->lf_xy = nullptr; ctx->lf_bits = nullptr;
-    double *d_xy = nullptr;
-    uint32_t *d_bits = nullptr;
-    if (dev_alloc(ctx, &d_xy, xy.size())) return -1;
-    if (dev_alloc(ctx, &d_bits, (size_t)n_word)) { (void)hipFree(d_xy); return -1; }
-    ctx->lf_xy = d_xy; ctx->lf_bits = d_bits;
-    HIPCHK(ctx, copy_sync(ctx->stream, d_xy, xy.data(), sizeof(double) * xy.size(), hipMemcpyHostToDevice));
-    HIPCHK(ctx, copy_sync(ctx->stream, d_bits, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice));
+    // (a new grid starts from nothing: a failure below leaves "no land grid")
+    ctx->an.lf_xy.reset(); ctx->an.lf_bits.reset();
+    if (ctx->an.lf_xy.upload(ctx, xy.data(), xy.size())) return -1;
+    if (ctx->an.lf_bits.upload(ctx, bits.data(), bits.size())) { ctx->an.lf_xy.reset(); return -1; }
     const double *lon = grid->lon, *lat = grid->lat;
-    ctx->lf_nlon = nlon; ctx->lf_nlat = nlat;
-    ctx->lf_periodic = lon[nlon - 1] - lon[0] + (lon[1] - lon[0]) == 360.0;
-    ctx->lf_guess[0] = lon[0]; ctx->lf_guess[1] = (double)(nlon - 1) / (lon[nlon - 1] - lon[0]);
-    ctx->lf_guess[2] = lat[0]; ctx->lf_guess[3] = (double)(nlat - 1) / (lat[nlat - 1] - lat[0]);
+    ctx->an.lf_nlon = nlon; ctx->an.lf_nlat = nlat;
+    ctx->an.lf_periodic = lon[nlon - 1] - lon[0] + (lon[1] - lon[0]) == 360.0;
+    ctx->an.lf_guess[0] = lon[0]; ctx->an.lf_guess[1] = (double)(nlon - 1) / (lon[nlon - 1] - lon[0]);
+    ctx->an.lf_guess[2] = lat[0]; ctx->an.lf_guess[3] = (double)(nlat - 1) / (lat[nlat - 1] - lat[0]);
     return 0;
 }
 
@@ -202,30 +197,28 @@ int tcr_land_info(tcr_ctx *ctx, int64_t *nlon, int64_t *nlat, int32_t *periodic)
 {
     if (!ctx) return -1;
     if (!nlon || !nlat || !periodic) return fail(ctx, "tcr_land_info: NULL argument");
-    if (!ctx->lf_xy) return fail(ctx, "tcr_land_info: no land grid on this context (tcr_land_upload)");
-    *nlon = ctx->lf_nlon; *nlat = ctx->lf_nlat; *periodic = ctx->lf_periodic ? 1 : 0;
+    if (!ctx->an.lf_xy.p) return fail(ctx, "tcr_land_info: no land grid on this context (tcr_land_upload)");
+    *nlon = ctx->an.lf_nlon; *nlat = ctx->an.lf_nlat; *periodic = ctx->an.lf_periodic ? 1 : 0;
     return 0;
 }
 
 int tcr_landfall_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, int32_t max_events, int32_t *n_landfall, int32_t *ev_k,
                      double *ev_lon, double *ev_lat, double *ev_v, double *ev_v_inland, uint8_t *flags, void *stream_)
 {
-    if (!ctx) return -1;
-    if (landfall_check(ctx, t, max_events, n_landfall, ev_k, ev_lon, ev_lat, ev_v, ev_v_inland)) return -1;
+    hipStream_t st = enter(ctx, stream_);
+    if (!st || landfall_check(ctx, t, max_events, n_landfall, ev_k, ev_lon, ev_lat, ev_v, ev_v_inland)) return -1;
     if (t->n_trk == 0) return 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
     LfArgs a{};
-    a.g.xy = ctx->lf_xy; a.g.bits = ctx->lf_bits;
-    a.g.nlon = (int32_t)ctx->lf_nlon; a.g.nlat = (int32_t)ctx->lf_nlat; a.g.periodic = ctx->lf_periodic ? 1 : 0;
-    a.g.lon0 = ctx->lf_guess[0]; a.g.lon_inv = ctx->lf_guess[1]; a.g.lat0 = ctx->lf_guess[2]; a.g.lat_inv = ctx->lf_guess[3];
+    a.g.xy = ctx->an.lf_xy.p; a.g.bits = ctx->an.lf_bits.p;
+    a.g.nlon = (int32_t)ctx->an.lf_nlon; a.g.nlat = (int32_t)ctx->an.lf_nlat; a.g.periodic = ctx->an.lf_periodic ? 1 : 0;
+    a.g.lon0 = ctx->an.lf_guess[0]; a.g.lon_inv = ctx->an.lf_guess[1]; a.g.lat0 = ctx->an.lf_guess[2]; a.g.lat_inv = ctx->an.lf_guess[3];
     a.lon = t->lon; a.lat = t->lat; a.vmax = t->vmax;
     a.n_trk = t->n_trk; a.n_t = t->n_t; a.stride = t->row_stride;
     a.max_events = max_events;
     a.n_lf = n_landfall; a.ev_k = ev_k; a.ev_lon = ev_lon; a.ev_lat = ev_lat; a.ev_v = ev_v; a.ev_vin = ev_v_inland;
     a.flags = flags;
     const unsigned blocks = (unsigned)std::min<int64_t>(kLfBlocksMax, (t->n_trk + kLfWaves - 1) / kLfWaves);
-    const int64_t n_xy = ctx->lf_nlon + ctx->lf_nlat;
+    const int64_t n_xy = ctx->an.lf_nlon + ctx->an.lf_nlat;
     if (n_xy <= kLfLdsMax)
         hipLaunchKernelGGL(k_landfall<true>, dim3(blocks), dim3(64 * kLfWaves), sizeof(double) * n_xy, st, a);
     else
@@ -237,10 +230,8 @@ int tcr_landfall_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, int32_t max_event
 int tcr_landfall_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, int32_t max_events, int32_t *n_landfall, int32_t *ev_k,
                       double *ev_lon, double *ev_lat, double *ev_v, double *ev_v_inland, uint8_t *flags)
 {
-    if (!ctx) return -1;
-    if (landfall_check(ctx, t, max_events, n_landfall, ev_k, ev_lon, ev_lat, ev_v, ev_v_inland)) return -1;
+    if (!enter(ctx) || landfall_check(ctx, t, max_events, n_landfall, ev_k, ev_lon, ev_lat, ev_v, ev_v_inland)) return -1;
     if (t->n_trk == 0) return 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
     const size_t n_ev = (size_t)t->n_trk * max_events, n_fl = (size_t)t->n_trk * t->n_t;
     tcr_hazard_tracks d;

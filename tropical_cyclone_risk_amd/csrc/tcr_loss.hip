@@ -112,18 +112,18 @@ int tcr_loss_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params *
         return -1;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
-    ScanWs &w = ctx->ls;
+    ScanWs &w = ctx->an.ls;
     const int64_t n_trk = t->n_trk, n_tile = (n_site + 63) / 64;
     std::vector<int64_t> tab, gch;
     scan_chunks(t, n_tile, tab, gch);                   // scan_run's own table: the sizes of the two loss workspaces
     const int64_t n_chunk = (int64_t)tab.size() / 3;
     if (n_tile * std::max<int64_t>(1, n_trk) >= ((int64_t)1 << 40) ||
-        scan_grow<double>(ctx, w, 6, (size_t)std::max<int64_t>(1, n_tile * n_trk)) ||
-        scan_grow<double>(ctx, w, 7, (size_t)std::max<int64_t>(1, n_chunk * n_site))) {
+        w.d[6].grow(ctx, sizeof(double) * (size_t)std::max<int64_t>(1, n_tile * n_trk)) < 0 ||
+        w.d[7].grow(ctx, sizeof(double) * (size_t)std::max<int64_t>(1, n_chunk * n_site)) < 0) {
         (void)hipGetLastError();
         return fail(ctx, "tcr_loss: the tile-loss workspace (sites / 64 x storms doubles) does not fit; split the sites");
     }
-    double *tile_loss = static_cast<double *>(w.d[6]), *site_part = static_cast<double *>(w.d[7]);
+    double *tile_loss = reinterpret_cast<double *>(w.d[6].p), *site_part = reinterpret_cast<double *>(w.d[7].p);
     const int64_t n_rec = (t->n_t - 1) * prm->substeps + 1;
     const size_t n_stage = (size_t)std::max<int64_t>(1, n_trk * t->n_t);
     const double c = prm->ck_cd;
@@ -137,7 +137,7 @@ int tcr_loss_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params *
                                 LossScan<false>{{c, 2.0 - c, 1.0 / (2.0 - c)}, site_value, site_v_half, lp->v_thresh, lp->v_half, tile_loss, site_part});
     });
     if (rc) return rc;
-    const int64_t *d_tab = static_cast<const int64_t *>(w.d[4]);
+    const int64_t *d_tab = reinterpret_cast<const int64_t *>(w.d[4].p);
     if (n_trk > 0)
         hipLaunchKernelGGL(k_loss_events, dim3((unsigned)((n_trk + 255) / 256)), dim3(256), 0, st, tile_loss, n_tile, n_trk, event_loss);
     hipLaunchKernelGGL(k_loss_years, dim3((unsigned)t->n_group), dim3(64), 0, st, event_loss, d_tab, d_tab + tab.size(), year_agg,

@@ -144,12 +144,10 @@ extern "C" {
 int tcr_rainfall_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, const tcr_rain_params *prm, int64_t n_site, const double *site_lon,
                      const double *site_lat, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_value, void *stream_)
 {
-    if (!ctx) return -1;
-    if (rainfall_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    hipStream_t st = enter(ctx, stream_);
+    if (!st || rainfall_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
     const int64_t n_rec = (t->n_t - 1) * prm->substeps + 1;
-    return scan_run<RfRec>(ctx, ctx->rf, "tcr_rainfall", t, n_rec, 0, n_site, site_lon, site_lat, prm->r_out_km, kWfEarthR / 1000.0,
+    return scan_run<RfRec>(ctx, ctx->an.rf, "tcr_rainfall", t, n_rec, 0, n_site, site_lon, site_lat, prm->r_out_km, kWfEarthR / 1000.0,
                            n_bin, thresholds, counts, site_value, st, [&](const ScanArgs<RfRec> &m, void *, dim3 grid, size_t lds) {
         RfPrepArgs p{t->lon, t->lat, t->vmax, t->n_trk, t->n_t, t->row_stride, prm->dt_s / (3600.0 * prm->substeps), prm->v_lo_kt,
                      prm->v_hi_kt, {prm->a[0], prm->a[1], prm->a[2], prm->a[3]}, {prm->b[0], prm->b[1], prm->b[2], prm->b[3]},
@@ -162,9 +160,7 @@ int tcr_rainfall_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, const tcr_rain_pa
 int tcr_rainfall_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, const tcr_rain_params *prm, int64_t n_site, const double *site_lon,
                       const double *site_lat, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_value)
 {
-    if (!ctx) return -1;
-    if (rainfall_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!enter(ctx) || rainfall_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
     DevBuf B;
     tcr_hazard_tracks d;
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, n_bin, site_value != nullptr);
@@ -173,6 +169,6 @@ int tcr_rainfall_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, const tcr_rain_p
     return scan_download(ctx, io, counts, site_value);
 }
 
-int tcr_rainfall_pairs(tcr_ctx *ctx, int64_t *pairs) { return ctx ? scan_pairs(ctx, ctx->rf, "tcr_rainfall", pairs) : -1; }
+int tcr_rainfall_pairs(tcr_ctx *ctx, int64_t *pairs) { return ctx ? scan_pairs(ctx, ctx->an.rf, "tcr_rainfall", pairs) : -1; }
 
 }  // extern "C"

@@ -225,11 +225,9 @@ extern "C" {
 int tcr_select_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, int32_t n_rank,
                    const int64_t *ranks, double *level, int32_t *n_valid, void *stream_)
 {
-    if (!ctx) return -1;
-    if (select_check(ctx, plane, n_row, n_col, row_stride, n_rank, ranks, level)) return -1;
+    hipStream_t st = enter(ctx, stream_);
+    if (!st || select_check(ctx, plane, n_row, n_col, row_stride, n_rank, ranks, level)) return -1;
     if (n_row == 0) return 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
     SelArgs a{};
     a.plane = plane; a.n_row = n_row; a.n_col = n_col; a.stride = row_stride; a.level = level; a.n_valid = n_valid; a.n_rank = n_rank;
     for (int j = 0; j < n_rank; ++j) a.ranks[j] = ranks[j];
@@ -241,10 +239,8 @@ int tcr_select_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_c
 int tcr_select_host(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, int32_t n_rank,
                     const int64_t *ranks, double *level, int32_t *n_valid)
 {
-    if (!ctx) return -1;
-    if (select_check(ctx, plane, n_row, n_col, row_stride, n_rank, ranks, level)) return -1;
+    if (!enter(ctx) || select_check(ctx, plane, n_row, n_col, row_stride, n_rank, ranks, level)) return -1;
     if (n_row == 0) return 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
     const size_t n_in = (size_t)(n_row - 1) * (size_t)row_stride + (size_t)n_col, n_out = (size_t)n_row * (size_t)n_rank;
     const double *d_plane = B.put(plane, n_in);

@@ -347,19 +347,8 @@ __global__ __launch_bounds__(256) void k_hazard_reduce(const int32_t *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-// ScanWs::d: 0 records, 1 caps (storms, then segments), 2 record counts, 3 partial counts, 4 chunk table + pair counter,
-// 5 the prep kernel's own workspace, 6 and 7 the analysis's own (tcr_loss.hip: tile losses, per-chunk site losses)
-template <typename T>
-int scan_grow(tcr_ctx *ctx, ScanWs &w, int i, size_t count)
-{
-    if (w.cap[i] >= count * sizeof(T)) return 0;
-    (void)hipFree(w.d[i]);
-    w.d[i] = nullptr; w.cap[i] = 0;
-    T *p = nullptr;
-    if (dev_alloc(ctx, &p, count)) return -1;
-    w.d[i] = p; w.cap[i] = count * sizeof(T);
-    return 0;
-}
+// ScanWs::d (blocks in bytes): 0 records, 1 caps (storms, then segments), 2 record counts, 3 partial counts, 4 chunk table + pair
+// counter, 5 the prep kernel's own workspace, 6 and 7 the analysis's own (tcr_loss.hip: tile losses, per-chunk site losses)
 
 // the arguments every analysis has; `who` is the entry point's prefix ("tcr_hazard"), n_t_rule its bound on n_t in words
 template <class Tracks>
@@ -421,12 +410,12 @@ int scan_run(tcr_ctx *ctx, ScanWs &w, const char *who, const Tracks *t, int64_t 
         return fail(ctx, "%s: too many sites x storm chunks for one launch; split the sites", who);
     const size_t n_tab = tab.size() + gch.size();
 
-    if (scan_grow<Rec>(ctx, w, 0, (size_t)std::max<int64_t>(1, n_trk * n_seg_max * kHzSeg)) ||
-        scan_grow<HzCap>(ctx, w, 1, (size_t)std::max<int64_t>(1, n_trk * (n_seg_max + 1))) ||
-        scan_grow<int32_t>(ctx, w, 2, (size_t)std::max<int64_t>(1, n_trk)) ||
-        scan_grow<int32_t>(ctx, w, 3, (size_t)std::max<int64_t>(1, n_chunk * n_site * n_bin)) ||
-        scan_grow<int64_t>(ctx, w, 4, n_tab + 1) ||
-        (extra_bytes && scan_grow<char>(ctx, w, 5, extra_bytes)))
+    if (w.d[0].grow(ctx, sizeof(Rec) * (size_t)std::max<int64_t>(1, n_trk * n_seg_max * kHzSeg)) < 0 ||
+        w.d[1].grow(ctx, sizeof(HzCap) * (size_t)std::max<int64_t>(1, n_trk * (n_seg_max + 1))) < 0 ||
+        w.d[2].grow(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(1, n_trk)) < 0 ||
+        w.d[3].grow(ctx, sizeof(int32_t) * (size_t)std::max<int64_t>(1, n_chunk * n_site * n_bin)) < 0 ||
+        w.d[4].grow(ctx, sizeof(int64_t) * (n_tab + 1)) < 0 ||
+        (extra_bytes && w.d[5].grow(ctx, extra_bytes) < 0))
         return -1;
     // the chunk table goes up through a pinned buffer of the workspace; the previous call's upload must be done with it
     if (w.ev) HIPCHK(ctx, hipEventSynchronize(w.ev));
@@ -434,26 +423,21 @@ int scan_run(tcr_ctx *ctx, ScanWs &w, const char *who, const Tracks *t, int64_t 
         HIPCHK(ctx, hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
         HIPCHK(ctx, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
     }
-    if (w.h_cap < n_tab) {
-        if (w.h) (void)hipHostFree(w.h);
-        w.h = nullptr; w.h_cap = 0;
-        HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void **>(&w.h), n_tab * sizeof(int64_t)));
-        w.h_cap = n_tab;
-    }
-    memcpy(w.h, tab.data(), tab.size() * sizeof(int64_t));
-    memcpy(w.h + tab.size(), gch.data(), gch.size() * sizeof(int64_t));
-    int64_t *d_tab = static_cast<int64_t *>(w.d[4]);
+    if (w.h.cap < n_tab) HIPCHK(ctx, w.h.alloc(n_tab));
+    memcpy(w.h.p, tab.data(), tab.size() * sizeof(int64_t));
+    memcpy(w.h.p + tab.size(), gch.data(), gch.size() * sizeof(int64_t));
+    int64_t *d_tab = reinterpret_cast<int64_t *>(w.d[4].p);
     unsigned long long *d_pairs = reinterpret_cast<unsigned long long *>(d_tab + n_tab);
-    HIPCHK(ctx, hipMemcpyAsync(d_tab, w.h, n_tab * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(d_tab, w.h.p, n_tab * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipEventRecord(w.ev, st));
     HIPCHK(ctx, hipMemsetAsync(d_pairs, 0, sizeof(unsigned long long), st));
     w.pairs = d_pairs;
 
-    HzCap *caps = static_cast<HzCap *>(w.d[1]);
-    int32_t *part = static_cast<int32_t *>(w.d[3]);
+    HzCap *caps = reinterpret_cast<HzCap *>(w.d[1].p);
+    int32_t *part = reinterpret_cast<int32_t *>(w.d[3].p);
     if (n_trk > 0) {                                    // (then every storm is in a chunk: n_chunk > 0)
         ScanArgs<Rec> m{};
-        m.rows = ScanRows<Rec>{static_cast<Rec *>(w.d[0]), caps + n_trk, caps, static_cast<int32_t *>(w.d[2]), n_seg_max};
+        m.rows = ScanRows<Rec>{reinterpret_cast<Rec *>(w.d[0].p), caps + n_trk, caps, reinterpret_cast<int32_t *>(w.d[2].p), n_seg_max};
         m.chunks = d_tab;
         m.site_lon = site_lon; m.site_lat = site_lat;
         m.n_site = n_site; m.n_tile = n_tile; m.n_trk = n_trk;
@@ -461,7 +445,7 @@ int scan_run(tcr_ctx *ctx, ScanWs &w, const char *who, const Tracks *t, int64_t 
         m.n_bin = n_bin;
         for (int b = 0; b < n_bin; ++b) m.thr[b] = thresholds[b];
         m.part = part; m.site_max = site_max; m.pairs = d_pairs;
-        HIPCHK(ctx, launch(m, w.d[5], dim3((unsigned)(n_tile * n_chunk)), sizeof(int32_t) * 64 * (n_bin + 1)));
+        HIPCHK(ctx, launch(m, w.d[5].p, dim3((unsigned)(n_tile * n_chunk)), sizeof(int32_t) * 64 * (n_bin + 1)));
     }
     const int64_t n_out = n_site * n_group * n_bin;
     hipLaunchKernelGGL(k_hazard_reduce, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, part, d_tab + tab.size(), n_site,

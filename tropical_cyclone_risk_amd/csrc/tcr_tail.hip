@@ -236,11 +236,9 @@ extern "C" {
 int tcr_tail_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, int32_t k, double total_years,
                  int32_t n_period, const double *periods, double *param, double *level, int32_t *n_valid, void *stream_)
 {
-    if (!ctx) return -1;
-    if (tail_check(ctx, plane, n_row, n_col, row_stride, k, total_years, n_period, periods, param, level)) return -1;
+    hipStream_t st = enter(ctx, stream_);
+    if (!st || tail_check(ctx, plane, n_row, n_col, row_stride, k, total_years, n_period, periods, param, level)) return -1;
     if (n_row == 0) return 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
     TailArgs a{};
     a.plane = plane; a.n_row = n_row; a.n_col = n_col; a.stride = row_stride; a.param = param; a.level = level; a.n_valid = n_valid;
     a.k = k; a.n_period = n_period;
@@ -253,10 +251,8 @@ int tcr_tail_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col
 int tcr_tail_host(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, int32_t k, double total_years,
                   int32_t n_period, const double *periods, double *param, double *level, int32_t *n_valid)
 {
-    if (!ctx) return -1;
-    if (tail_check(ctx, plane, n_row, n_col, row_stride, k, total_years, n_period, periods, param, level)) return -1;
+    if (!enter(ctx) || tail_check(ctx, plane, n_row, n_col, row_stride, k, total_years, n_period, periods, param, level)) return -1;
     if (n_row == 0) return 0;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
     const size_t n_in = (size_t)(n_row - 1) * (size_t)row_stride + (size_t)n_col, n_out = (size_t)n_row * (size_t)n_period;
     const double *d_plane = B.put(plane, n_in);

@@ -259,14 +259,12 @@ extern "C" {
 int tcr_windfield_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params *prm, int64_t n_site, const double *site_lon,
                       const double *site_lat, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_max, void *stream_)
 {
-    if (!ctx) return -1;
-    if (windfield_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
+    hipStream_t st = enter(ctx, stream_);
+    if (!st || windfield_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
     const int64_t n_rec = (t->n_t - 1) * prm->substeps + 1;
     const size_t n_stage = (size_t)std::max<int64_t>(1, t->n_trk * t->n_t);
     const double c = prm->ck_cd;
-    return scan_run<WfRec>(ctx, ctx->wf, "tcr_windfield", t, n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat, prm->r_out_km,
+    return scan_run<WfRec>(ctx, ctx->an.wf, "tcr_windfield", t, n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat, prm->r_out_km,
                            kWfEarthR / 1000.0, n_bin, thresholds, counts, site_max, st,
                            [&](const ScanArgs<WfRec> &m, void *stage, dim3 grid, size_t lds) {
         if (c == 1.0) return wind_scan_launch(t, prm, m, stage, grid, lds, st, WindScan<true>{c, 2.0 - c, 1.0 / (2.0 - c)});
@@ -277,10 +275,8 @@ int tcr_windfield_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_par
 int tcr_windfield_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params *prm, int64_t n_site, const double *site_lon,
                        const double *site_lat, int32_t n_bin, const double *thresholds, int32_t *counts, double *site_max)
 {
-    if (!ctx) return -1;
-    if (windfield_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
+    if (!enter(ctx) || windfield_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
     if (!wind_rmax_ok(t)) return fail(ctx, "tcr_windfield_host: rmax_km must be finite and > 0 at every sample of a track");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
     tcr_wind_tracks d;
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, n_bin, site_max != nullptr);
@@ -289,6 +285,6 @@ int tcr_windfield_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_pa
     return scan_download(ctx, io, counts, site_max);
 }
 
-int tcr_windfield_pairs(tcr_ctx *ctx, int64_t *pairs) { return ctx ? scan_pairs(ctx, ctx->wf, "tcr_windfield", pairs) : -1; }
+int tcr_windfield_pairs(tcr_ctx *ctx, int64_t *pairs) { return ctx ? scan_pairs(ctx, ctx->an.wf, "tcr_windfield", pairs) : -1; }
 
 }  // extern "C"
