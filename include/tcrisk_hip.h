@@ -789,6 +789,45 @@ int tcr_compound_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const double 
 /* (site, record) pairs the last tcr_compound_* call of this context evaluated after culling with the larger radius; waits for it */
 int tcr_compound_pairs(tcr_ctx *ctx, int64_t *pairs);
 
+/* ---- wind duration: hours at or above wind levels at sites ------------------------------------------------------------ */
+/* replaces: nothing in the reference's code; the "for how long" next to the footprint's "how strong": hours of gale-, storm- and
+ * hurricane-force wind per storm and per year, which downtime and outage models, parametric covers and fatigue-type damage work
+ * from.  The footprint's wind is evaluated once per (site, record) pair and time is accumulated for up to 8 levels at once.
+ *   track, records, sub-steps, inclusion and the wind of a (site, record) pair: those of the wind footprint above, bit for bit.
+ *                   The value compared with a level is the very double tcr_windfield_* takes the max of.
+ *   levels          n_level wind levels (m/s), 1 <= n_level <= 8, finite, > 0, strictly ascending.
+ *   weights         record q of a storm's n_rec records carries the half-weight h_q = 2, or 1 for q = 0 and q = n_rec - 1: the
+ *                   trapezoid rule in units of half a sub-step.  u = dt_s / (7200 substeps) is the hours per half-weight.
+ *   H[l][i][s]      the int32 sum of h_q over the included records of storm s at site i whose wind is >= levels[l].
+ *                   n_rec <= 2^26, so H < 2^28.
+ *   site_hours      a host array of n_level device pointers (host pointers in tcr_duration_host); the array may be NULL, and so may
+ *                   any entry (not written).  Entry l is a [n_site][n_trk] plane: (double)H[l][i][s] * u (one multiply); NaN where
+ *                   no record of the storm is included at the site (so at every level alike), 0.0 where records are included but
+ *                   none reaches the level.
+ *   counts          [n_site][n_group][n_level][n_bin] (int32): storms s in [group_off[g], group_off[g + 1]) with
+ *                   (double)H * u >= thresholds[b] (hours).  A NaN counts nowhere.
+ *   half_steps      [n_site][n_group][n_level] (int64, optional, NULL: not written): the sum of H over the storms of the group.
+ *                   Expected hours per year at or above a level: half_steps summed over the groups, times u / total_years.
+ * Arguments: tracks and prm under exactly the rules of tcr_windfield_*; 1 <= n_level <= 8 and the levels as above; thresholds
+ * finite, > 0 and strictly ascending; n_level * (n_bin + 1) <= 64.  Every message begins with "tcr_duration:".  rm > 0 and finite
+ * at every sample of a track: tcr_duration_host checks the rmax_km plane as tcr_windfield_host does; tcr_duration_dev cannot, and
+ * drops a storm with a bad rm (NaN at every site and level, counted nowhere).
+ * Not modelled: duration is quantised to dt_s / (2 substeps), and a crossing of a level between two records is not interpolated.
+ * Everything accumulated is an integer (that is what the half-weights are for: a sum of fp64 hours would depend on its order), so
+ * every output is bit-identical from run to run, whatever the launch shape, the site order, the storm order or the chunking.
+ * _dev: planes, sites, counts, half_steps and the planes site_hours points to are device memory, asynchronous on `stream`; levels,
+ * thresholds, group_off and the site_hours pointer array are host memory in both entry points.  The workspace is the context's
+ * sixth: calls of tcr_duration_* on one context must be ordered, but one may be in flight next to a tcr_hazard_*, tcr_windfield_*,
+ * tcr_loss_*, tcr_rainfall_* or tcr_compound_* call on another stream. */
+int tcr_duration_dev(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_wind_params *prm, int64_t n_site, const double *site_lon,
+                     const double *site_lat, int32_t n_level, const double *levels, int32_t n_bin, const double *thresholds,
+                     int32_t *counts, int64_t *half_steps, double *const *site_hours, void *stream);
+int tcr_duration_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_wind_params *prm, int64_t n_site, const double *site_lon,
+                      const double *site_lat, int32_t n_level, const double *levels, int32_t n_bin, const double *thresholds,
+                      int32_t *counts, int64_t *half_steps, double *const *site_hours);
+/* (site, record) pairs the last tcr_duration_* call of this context evaluated after culling; waits for that call */
+int tcr_duration_pairs(tcr_ctx *ctx, int64_t *pairs);
+
 /* ---- row selection (return levels): the k-th largest value of every row of a per-storm plane ----------------------------- */
 /* replaces: nothing in the reference's code; the inverse of the return periods above.  With return_period = total_years /
  * count(peak >= v), the level of period T at a site is the k-th largest storm peak there, k the smallest integer with

@@ -1,5 +1,5 @@
 // The site scan: what the per-site analyses of a track ensemble (tcr_hazard.hip, tcr_windfield.hip, tcr_loss.hip, tcr_rainfall.hip,
-// tcr_compound.hip) share.  Each of them turns
+// tcr_compound.hip, tcr_duration.hip) share.  Each of them turns
 // every storm into a row of wave-uniform records, and wants
 //
 //   site_max[site][storm] = max of value(site, record) over the storm's records with haversine(site, record) <= R   (NaN: none)
@@ -35,8 +35,22 @@
 //                   joint histogram's cells are kJointHist (16 bits), and the caller keeps a chunk at kJointMaxChunk storms or
 //                   fewer (scan_run's max_chunk), which no cell and no suffix sum can exceed.
 //                   kJoint with kLoss or kSum is a static_assert.  Policies without kJoint compile to the code they had before it.
-// and calls scan_run with a workspace of its own (ScanWs, five instances in tcr_ctx: a hazard, a footprint, a loss, a rainfall and
-// a compound call may be in flight on different streams of one context).
+//                   A policy with `static constexpr int kLevels = N` (1 <= N <= kScanMaxLevel; tcr_duration.hip) measures time
+//                   instead of a peak: value(site, record, a) is formed once per included pair and compared with the policy's N
+//                   ascending level[] (unused ones +inf), and the record's integer weight(record) is added to the int32
+//                   accumulator of every level the value reaches (>=) and to one more that counts the included records.  The N + 1
+//                   accumulators are registers: fixed arrays, fully unrolled, never indexed by a run-time value.  Per storm each
+//                   of the policy's n_level levels has the value (double)sum * unit (NaN when no record was included), which the
+//                   lane that accumulated it writes to the policy's site_level[l] (when not NULL) and ranks against the n_hbin
+//                   thresholds in thr into the level's own (n_hbin + 1) cells of the histogram, which therefore has
+//                   n_level (n_hbin + 1) cells: the caller passes n_bin = n_level n_hbin (the partial counts it gets,
+//                   [level][threshold], which k_hazard_reduce sums unchanged) and launches with LDS for those cells instead of the
+//                   bytes it is handed.  Every lane also keeps an int64 total of its sums per level over the chunk's storms and
+//                   writes it to the policy's level_part [n_chunk][n_site][n_level].  There is no max: the caller passes site_max = NULL.
+//                   kLevels with kLoss, kSum or kJoint is a static_assert.  Policies without kLevels compile to the code they had
+//                   before it existed.
+// and calls scan_run with a workspace of its own (ScanWs, six instances in tcr_ctx: a hazard, a footprint, a loss, a rainfall, a
+// compound and a duration call may be in flight on different streams of one context).
 //
 //   k_site_scan      one wave per (tile of 64 sites, chunk of storms of one group): every lane holds one site's terms in registers;
 //                    the records are wave-uniform and come through scalar loads.  A storm or segment whose cap is farther than R
@@ -61,11 +75,16 @@
 // the values come from the functions the single-hazard policies call, on the same record terms and the same angle expression.  So
 // each plane is bit for bit what the single-hazard scan of that policy writes, and the 2-D counts are integer sums of per-storm
 // ranks of those values: bit-identical whatever the launch shape, the site order and the storm order.
+//
+// And for a kLevels policy, by the first argument alone: everything it accumulates is an integer.  A pair's value and weight do not
+// depend on the other pairs, a skipped pair is never an included one, and int32 and int64 sums do not depend on order; the value
+// written is one conversion and one multiply of such a sum.
 
 namespace {
 
 constexpr int kHzSeg = 32;                  // records per culling segment
 constexpr int kHzMaxBin = 64;
+constexpr int kScanMaxLevel = 8;            // levels of a kLevels policy
 using kJointHist = uint16_t;                // a cell of the joint scan's LDS histogram
 constexpr int64_t kJointMaxChunk = 65535;   // storms of a chunk it can count
 constexpr double kHzPad = 1e-9;             // radians added to every cap radius
@@ -153,6 +172,12 @@ struct scan_has_joint : std::false_type {};
 template <class P>
 struct scan_has_joint<P, std::void_t<decltype(P::kJoint)>> : std::bool_constant<P::kJoint> {};
 
+// Policy::kLevels (the number of level accumulators) when the policy has one, 0 otherwise
+template <class P, class = void>
+struct scan_levels : std::integral_constant<int, 0> {};
+template <class P>
+struct scan_levels<P, std::void_t<decltype(P::kLevels)>> : std::integral_constant<int, P::kLevels> {};
+
 // the number of the n ascending thresholds thr that are <= m (0 for a NaN: no comparison holds): the joint scan's two ranks
 __device__ __forceinline__ int scan_rank(const double *thr, int n, double m)
 {
@@ -235,7 +260,13 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
     const double y = a.site_lat[my], x = a.site_lon[my];
     const double hp = y * (kPi / 360.0), hl = x * (kPi / 360.0), phi = y * (kPi / 180.0), lam = x * (kPi / 180.0);
     const ScanSite me{sin(hp), cos(hp), sin(hl), cos(hl), cos(phi), sin(phi), sin(lam), cos(lam)};
-    for (int k = 0; k <= a.n_bin; ++k) hist[k * 64 + lane] = 0;
+    constexpr int kLevels = scan_levels<Policy>::value;
+    static_assert(kLevels >= 0 && kLevels <= kScanMaxLevel, "a kLevels policy has 1 to kScanMaxLevel level accumulators");
+    if constexpr (kLevels > 0) {                        // kLevels: [n_level][n_hbin + 1][64]
+        for (int k = 0; k < pol.n_level * (pol.n_hbin + 1); ++k) hist[k * 64 + lane] = 0;
+    } else {
+        for (int k = 0; k <= a.n_bin; ++k) hist[k * 64 + lane] = 0;
+    }
 
     // tile cap: centre = the tile's first site, radius = the largest angle from it, padded by R
     const double sp0 = __shfl(me.sp, 0, 64), cp0 = __shfl(me.cp, 0, 64), sl0 = __shfl(me.sl, 0, 64), cl0 = __shfl(me.cl, 0, 64);
@@ -253,6 +284,9 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
     static_assert(!(kSum && kLoss), "the loss variant of the scan is defined on a max");
     constexpr bool kJoint = scan_has_joint<Policy>::value;
     static_assert(!(kJoint && (kLoss || kSum)), "the joint scan has accumulators of its own: neither the loss nor the sum variant");
+    static_assert(!(kLevels > 0 && (kLoss || kSum || kJoint)), "the level scan accumulates weights, not values: no other variant");
+    constexpr int kNL = kLevels > 0 ? kLevels : 1;
+    [[maybe_unused]] int64_t lv_total[kNL] = {};        // kLevels: this site's sums of the chunk's storms, per level
     [[maybe_unused]] double loss_acc = 0.0;             // kLoss: this site's losses of the chunk's storms, summed in storm order
     [[maybe_unused]] auto terms = [&] { if constexpr (kLoss) return pol.site_terms(my, valid); else return 0; }();
     __syncthreads();
@@ -260,6 +294,8 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
         double m = NAN;
         [[maybe_unused]] double m2 = NAN;               // kJoint: the second hazard
         [[maybe_unused]] bool near = false;             // kLoss: the storm's cap reaches the tile (wave-uniform)
+        [[maybe_unused]] int32_t lv[kNL] = {};          // kLevels: the weights of the records that reach each level,
+        [[maybe_unused]] int32_t lv_in = 0;             // and of every included record
         const int n = hz_uniform(a.rows.cnt + s);
         if (n > 0 && !hz_far(hz_uniform(a.rows.storm + s), tx, ty, tz, ct, st, rt)) {
             if constexpr (kLoss) near = true;
@@ -283,6 +319,14 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
                                 else m2 = fmax(m2, v);
                             }
                         }
+                    } else if constexpr (kLevels > 0) {
+                        if (q <= a.a_R) {
+                            const double v = pol.value(me, p, q);
+                            const int32_t h = pol.weight(p);
+                            lv_in += h;
+#pragma unroll
+                            for (int l = 0; l < kNL; ++l) lv[l] += v >= pol.level[l] ? h : 0;         // (a NaN reaches none)
+                        }
                     } else if constexpr (kSum) {
                         if (q <= a.a_R) { const double v = pol.value(me, p, q); m = isnan(m) ? v : m + v; }   // in record order
                     } else {
@@ -304,7 +348,17 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
             }
             if (lane == 0) pol.tile_loss[tile * a.n_trk + s] = t;
         }
-        if constexpr (kJoint) {                         // every storm is counted: a NaN has rank 0
+        if constexpr (kLevels > 0) {                    // a plane and a rank per level; a storm without an included record counts nowhere
+#pragma unroll
+            for (int l = 0; l < kNL; ++l) {
+                if (l < pol.n_level) {                  // (wave-uniform)
+                    const double d = lv_in ? (double)lv[l] * pol.unit : NAN;
+                    if (pol.site_level[l] && valid) pol.site_level[l][site * a.n_trk + s] = d;
+                    if (lv_in) hist[(l * (pol.n_hbin + 1) + scan_rank(a.thr, pol.n_hbin, d)) * 64 + lane] += 1;
+                    lv_total[l] += lv[l];
+                }
+            }
+        } else if constexpr (kJoint) {                  // every storm is counted: a NaN has rank 0
             const int kw = scan_rank(a.thr, pol.n_first, m), kr = scan_rank(a.thr + pol.n_first, pol.n_second, m2);
             hist[(kw * (pol.n_second + 1) + kr) * 64 + lane] += 1;
         } else if (!isnan(m)) {
@@ -324,7 +378,15 @@ __global__ __launch_bounds__(64) void k_site_scan(ScanArgs<typename Policy::Rec>
     if (valid) {
         [[maybe_unused]] int32_t c = 0;
         int32_t *out = a.part + (chunk * a.n_site + site) * a.n_bin;
-        if constexpr (kJoint) {
+        if constexpr (kLevels > 0) {                    // at least b + 1 thresholds, per level; and the level's total
+            for (int l = 0; l < pol.n_level; ++l) {
+                int32_t cl = 0;
+                for (int b = pol.n_hbin - 1; b >= 0; --b) { cl += hist[(l * (pol.n_hbin + 1) + b + 1) * 64 + lane]; out[l * pol.n_hbin + b] = cl; }
+            }
+#pragma unroll
+            for (int l = 0; l < kNL; ++l)
+                if (l < pol.n_level) pol.level_part[(chunk * a.n_site + site) * pol.n_level + l] = lv_total[l];
+        } else if constexpr (kJoint) {
             for (int b = 0; b < a.n_bin; ++b) out[b] = hist[b * 64 + lane];
         } else {
             for (int b = a.n_bin - 1; b >= 0; --b) { c += hist[(b + 1) * 64 + lane]; out[b] = c; }
@@ -348,7 +410,8 @@ __global__ __launch_bounds__(256) void k_hazard_reduce(const int32_t *__restrict
 
 // ---------------------------------------------------------------------------------------------------------------- host
 // ScanWs::d (blocks in bytes): 0 records, 1 caps (storms, then segments), 2 record counts, 3 partial counts, 4 chunk table + pair
-// counter, 5 the prep kernel's own workspace, 6 and 7 the analysis's own (tcr_loss.hip: tile losses, per-chunk site losses)
+// counter, 5 the prep kernel's own workspace, 6 and 7 the analysis's own (tcr_loss.hip: tile losses, per-chunk site losses;
+// tcr_duration.hip: 6 the per-chunk level totals)
 
 // the arguments every analysis has; `who` is the entry point's prefix ("tcr_hazard"), n_t_rule its bound on n_t in words
 template <class Tracks>

@@ -8,7 +8,7 @@
 // A user of the site scan (tcr_sitescan.h: tiling, culling, counts).  What is the footprint's own:
 //   k_wind_prep      one wave per storm: finds the track (ballot), stages (lon, lat, v, rm, A) of every track sample with the
 //                    translation speed in the operation order of vmax_at (tcr_kernels.hip), then writes one record per sample and
-//                    sub-sample with every wave-uniform term a pair needs; the scan's row tail writes the bounding caps of the
+//                    sub-sample with every wave-uniform term a pair needs (and its trapezoid half-weight); the scan's row tail writes the bounding caps of the
 //                    storm and of every kHzSeg-record segment;
 //   WindScan<c == 1> the policy of k_site_scan: the scan tests the haversine argument a against a_out first (no trigonometry), so
 //                    only included lanes pay for asin, the square roots and the profile.
@@ -33,9 +33,10 @@ constexpr double kWfOmega = 7.292e-5;               // s^-1
 
 struct WfStage { double lon, lat, v, rm, ae, an, pad0, pad1; };      // one track sample (64 bytes)
 // one sample or sub-sample (128 bytes): half-angle terms of the centre (distance), full-angle terms (direction), rm (m), Mm, f / 2,
-// 1 + |A / v|^2 and b = 2 h A / v
+// 1 + |A / v|^2 and b = 2 h A / v; then hw, which k_wind_prep fills with the record's trapezoid half-weight (an int64 in the slot's
+// bits: 2, or 1 for a track's first and last record) and only tcr_duration.hip reads: uniform() does not load it
 struct WfRec {
-    double sp, cp, sl, cl, cosp, sinp, sinl, cosl, rm, mm, f2, a2, be, bn, pad0, pad1;
+    double sp, cp, sl, cl, cosp, sinp, sinl, cosl, rm, mm, f2, a2, be, bn, hw, pad1;
     static __device__ __forceinline__ WfRec uniform(const WfRec *p)
     {
         const double *d = &p->sp;
@@ -96,7 +97,7 @@ __device__ __forceinline__ WfRec wf_record(double x, double y, double v, double 
     r.sp = sin(hp); r.cp = cos(hp); r.sl = sin(hl); r.cl = cos(hl);
     r.cosp = cos(phi); r.sinp = sin(phi); r.sinl = sin(lam); r.cosl = cos(lam);
     r.rm = rm_km * 1000.0;
-    r.pad0 = r.pad1 = 0.0;
+    r.hw = r.pad1 = 0.0;
     if (v > 0.0) {
         const double f2 = kWfOmega * fabs(r.sinp);          // f / 2
         const double h2 = y >= 0.0 ? 2.0 : -2.0;            // 2 h
@@ -162,7 +163,11 @@ __global__ __launch_bounds__(64) void k_wind_prep(WfPrepArgs a)
     const bool drop = __ballot(bad_rm) != 0;
     const int nr = (n >= 2 && !drop) ? (int)((n - 1) * a.sub + 1) : 0;
     __syncthreads();                                    // the records read stage entries other lanes wrote
-    for (int q = lane; q < nr; q += 64) row[q] = wf_sub_record(st, q, a.sub);
+    for (int q = lane; q < nr; q += 64) {
+        WfRec r = wf_sub_record(st, q, a.sub);
+        r.hw = __longlong_as_double(q == 0 || q == nr - 1 ? 1 : 2);
+        row[q] = r;
+    }
     scan_finish_row(a.out, s, nr);
 }
 

@@ -1,0 +1,203 @@
+"""Wind duration: for how long every storm of a track ensemble brings every site a wind of at least each of a few levels, how
+often it does so for at least so many hours, and the expected hours per year.
+
+The wind is the footprint's (``windfield.py``): the same track, records, sub-steps, outer radius and per-pair wind, bit for bit.
+On the GPU (``csrc/tcr_duration.hip``) it is evaluated once per (site, record) pair and compared with all levels at once:
+
+1. record ``q`` of a storm carries the integer half-weight 2, or 1 at the two ends of the track (the trapezoid rule in units of
+   half a sub-step); ``H`` is the sum of the half-weights of the records within ``r_out_km`` of the site whose wind is ``>=`` the
+   level, and the storm's hours there are ``H * hours_per_half_step`` with ``hours_per_half_step = dt_s / (7200 substeps)``
+   (NaN when no record is within ``r_out_km``, 0 when none reaches the level);
+2. per group of storms (a year, or an (ensemble file, year) pair) and level, the number of storms whose hours are ``>=`` each of
+   the ascending duration thresholds, and the sum of ``H`` (``half_steps``): the hours per year at or above a level are
+   ``half_steps.sum(groups) * hours_per_half_step / total_years``;
+3. the return period ``total_years / exceedance_count`` (``hazard.return_periods``).
+
+Everything accumulated is an integer, so every output is bit-identical whatever the site order, the storm order and the launch
+shape.  The contract is the header's "wind duration" section (include/tcrisk_hip.h).  Not modelled: duration is quantised to
+``dt_s / (2 substeps)``, and a crossing of a level between two records is not interpolated.
+
+    python -m tropical_cyclone_risk_amd.duration TRACKS.nc [TRACKS_e0.nc ...] --site=-80.1918,25.7617 --out duration.npz
+
+With ``--return-periods 10,50,100`` also the inverse, the hours of those return periods at every site and level (levels.py).
+"""
+import argparse
+import ctypes as C
+import sys
+
+import numpy as np
+
+from . import _lib, analysis, hazard, windfield
+from .sitescan import site_scan
+
+MAX_LEVELS = 8
+MAX_CELLS = 64
+DEFAULT_LEVELS = np.array([34.0, 50.0, 64.0]) * 1852.0 / 3600.0          # gale, storm and hurricane force (kt) in m/s
+DEFAULT_HOURS = np.array([1, 3, 6, 12, 24, 48], dtype=np.float64)
+
+
+def hours_per_half_step(dt_s, substeps):
+    """u of the contract: the hours one half-weight stands for."""
+    return float(dt_s) / (7200.0 * int(substeps))
+
+
+def site_duration(lon, lat, v, env, groups, site_lon, site_lat, dt_s, levels=DEFAULT_LEVELS, thresholds=DEFAULT_HOURS, rmax_km=None,
+                  ck_cd=None, r_out_km=500., substeps=1, return_hours=False, engine=None, device=0, n_groups=None):
+    """Hours at or above wind levels, their exceedance counts and their totals, at every site.
+
+    lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, groups, n_groups, site_lon / site_lat, engine, device: as
+    windfield.site_wind, under the same rules.  levels: 1 to 8 wind levels (m/s), finite, > 0, strictly ascending.  thresholds:
+    durations (hours), finite, > 0, strictly ascending; n_level * (n_bin + 1) <= 64.  return_hours: True, or a list of level
+    indices.  Returns a dict: ``counts`` [n_site][n_groups][n_level][n_bin] int32, ``half_steps`` [n_site][n_groups][n_level]
+    int64, ``hours_per_half_step``, ``levels``, ``thresholds``, and with ``return_hours`` ``site_hours``
+    [n_level][n_site][n_trk] (hours; NaN: no sample within r_out_km; all NaN for a level not asked for: a plane is
+    n_site * n_trk * 8 bytes on the device, which is why they are selectable), in the type and on the device of ``lon``.
+    """
+    lev, want = _check_levels(levels, thresholds, return_hours)
+    res, fl = _scan(lon, lat, v, env, groups, site_lon, site_lat, dt_s, lev, thresholds, rmax_km, ck_cd, r_out_km, substeps, want,
+                    engine, device, n_groups)
+    if return_hours is not False and return_hours is not None:
+        planes = res.pop('planes')
+        n_site, n_trk = int(res['counts'].shape[0]), int(lon.shape[0]) if hasattr(lon, 'shape') else len(lon)
+        out = fl.new((lev.size, n_site, n_trk), 'f8')
+        for l in range(lev.size):
+            out[l] = planes[l] if l in planes else np.nan
+        res['site_hours'] = out
+    else:
+        res.pop('planes')
+    return res
+
+
+def _check_levels(levels, thresholds, return_hours):
+    """The duration's own argument checks (ValueError): (levels, the sorted level indices whose planes are wanted)."""
+    lev = np.ascontiguousarray(np.asarray(levels, dtype=np.float64).reshape(-1))
+    if not 1 <= lev.size <= MAX_LEVELS:
+        raise ValueError('give 1 to %d levels' % MAX_LEVELS)
+    if not np.isfinite(lev).all() or np.any(lev <= 0) or np.any(np.diff(lev) <= 0):
+        raise ValueError('levels must be finite, > 0 and strictly ascending')
+    thr = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    if thr.size < 1 or not np.isfinite(thr).all() or np.any(thr <= 0) or np.any(np.diff(thr) <= 0):
+        raise ValueError('thresholds must be finite, > 0 and strictly ascending')
+    if lev.size * (thr.size + 1) > MAX_CELLS:
+        raise ValueError('n_level * (n_bin + 1) must be <= %d' % MAX_CELLS)
+    if return_hours is True:
+        want = list(range(lev.size))
+    elif return_hours is False or return_hours is None:
+        want = []
+    else:
+        try:
+            want = sorted({int(l) for l in return_hours if int(l) == l and not isinstance(l, bool)})
+            if len(want) != len(list(return_hours)):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError('return_hours must be True, False or a list of distinct level indices')
+        if any(not 0 <= l < lev.size for l in want):
+            raise ValueError('return_hours names a level that does not exist')
+    return lev, want
+
+
+def _scan(lon, lat, v, env, groups, site_lon, site_lat, dt_s, lev, thresholds, rmax_km, ck_cd, r_out_km, substeps, want, engine, device,
+          n_groups):
+    """One call of tcr_duration_*: (dict with ``planes`` = {level index: [n_site][n_trk] plane} for the levels in want, Flavour)."""
+    planes, fl, thr, prm = windfield._prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
+    n_level, n_bin = int(lev.size), int(thr.size)
+    outputs = [('half_steps', ('site_group', n_level))] + [('hours%d' % l, 'pair') for l in want]
+
+    def make_args(a):
+        n_bin_, thr_, counts_, _ = a.out
+        hours = (C.c_void_p * n_level)()
+        for l, p in zip(want, a.outputs[1:]):
+            hours[l] = p
+        return (C.byref(windfield._tracks_struct(a)), C.byref(prm)) + a.sites + \
+            (n_level, lev.ctypes.data_as(_lib.DP), n_bin_, thr_, counts_, a.outputs[0], hours if want else None)
+    res = site_scan('tcr_duration', planes, fl, groups, n_groups, site_lon, site_lat, thr, False, engine, device, make_args,
+                    more_outputs=outputs, count_cells=n_level * n_bin)
+    n_site, n_grp = int(res['counts'].shape[0]), int(res['counts'].shape[1])
+    res['counts'] = res['counts'].reshape(n_site, n_grp, n_level, n_bin)
+    res['planes'] = {l: res.pop('hours%d' % l) for l in want}
+    res['hours_per_half_step'] = hours_per_half_step(prm.dt_s, prm.substeps)
+    res['levels'] = lev
+    return res, fl
+
+
+# ---------------------------------------------------------------------------------------------------------------- CLI
+def _parse_levels(text):
+    try:
+        lev = np.array([float(x) for x in text.split(',')])
+    except ValueError:
+        raise argparse.ArgumentTypeError('--levels: expected L1,L2,... (m/s), got %r' % text)
+    return lev
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog='python -m tropical_cyclone_risk_amd.duration',
+                                description='Hours at or above wind levels at sites: exceedance counts of durations, their return '
+                                            'periods and the expected hours per year.')
+    analysis.add_site_args(p)
+    analysis.add_footprint_args(p)
+    p.add_argument('--levels', type=_parse_levels, default=DEFAULT_LEVELS, metavar='L1,L2,...',
+                   help='1 to 8 ascending wind levels in m/s (default: 34, 50 and 64 kt)')
+    p.add_argument('--thresholds', type=lambda t: analysis.parse_range(t, '--thresholds'), default=DEFAULT_HOURS, metavar='LO:HI:STEP',
+                   help='durations in hours (default: %s)' % ' '.join('%g' % t for t in DEFAULT_HOURS))
+    analysis.add_return_period_arg(p, 'hours at or above every level')
+    analysis.add_track_args(p, 'duration.npz')
+    a = p.parse_args(argv)
+    if a.tail_exceedances is not None:
+        p.error('--tail-exceedances is not offered for durations: they are quantised in half sub-steps, which a Pareto fit to '
+                'the excesses does not describe')
+    if not (a.site or a.sites or a.grid):
+        p.error('give sites with --site, --sites or --grid')
+    try:
+        _check_levels(a.levels, a.thresholds, False)
+    except ValueError as e:
+        p.error(str(e))
+    return a
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    site_lon, site_lat = analysis.collect_sites(args)
+    if site_lon.size == 0:
+        raise SystemExit('no sites')
+    lon, lat, _, v, env, groups, gfile, gyear, dt = analysis.load_wind_planes(args.tracks)
+    total_years = len(gfile)
+    kw = dict(rmax_km=args.rmax_km, ck_cd=args.ck_cd, r_out_km=args.r_out_km, substeps=args.substeps, n_groups=total_years)
+    res = site_duration(lon, lat, v, env, groups, site_lon, site_lat, dt, levels=args.levels, thresholds=args.thresholds,
+                        device=args.device, **kw)
+    u = res['hours_per_half_step']
+    annual = res['half_steps'].sum(axis=1) * u / total_years
+    more = {}
+    if args.return_periods is not None:
+        from . import levels as rl
+        lev = res['levels']
+        per_level = []
+        for l in range(lev.size):                           # one blocked pass per level, with that level's plane only
+            def one(t, x, y, l=l):
+                r, _ = _scan(t[0], t[1], t[2], t[3], groups, x, y, dt, lev, args.thresholds, kw['rmax_km'], kw['ck_cd'], kw['r_out_km'],
+                             kw['substeps'], [l], None, 0, total_years)
+                r['hours'] = r.pop('planes')[l]
+                return r
+            per_level.append(rl.device_levels(one, (lon, lat, v, tuple(env)), site_lon, site_lat, total_years, args.return_periods,
+                                              'hours', args.device))
+        more = dict(return_level=np.stack([r['return_level'] for r in per_level], axis=1), return_periods=per_level[0]['return_periods'],
+                    n_reach=per_level[0]['n_reach'])
+    rp = hazard.return_periods(res['counts'], total_years)
+    np.savez(args.out, counts=res['counts'], return_period=rp, annual_hours=annual, levels=res['levels'], thresholds=res['thresholds'],
+             site_lon=site_lon, site_lat=site_lat, total_years=total_years, dt_s=dt, **analysis.group_meta(args.tracks, gfile, gyear),
+             **more)
+    print('%d sites, %d storms, %d groups (%d files), total_years = %d, r_out = %g km, %d substeps -> %s'
+          % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.r_out_km, args.substeps, args.out))
+    if site_lon.size <= 10:
+        print('hours per year at or above (m/s): ' + ' '.join('%8.4g' % x for x in res['levels']))
+        for i in range(site_lon.size):
+            print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%8.4g' % x for x in annual[i]))
+        if more:
+            for l, x in enumerate(res['levels']):
+                print('hours at or above %.4g m/s by return period (years): ' % x + ' '.join('%6g' % t for t in more['return_periods']))
+                for i in range(site_lon.size):
+                    print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%6.4g' % h for h in more['return_level'][i, l]))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

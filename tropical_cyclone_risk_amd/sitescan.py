@@ -1,5 +1,5 @@
 """The Python side of the per-site scan (csrc/tcr_sitescan.h), which site hazard, wind footprint, portfolio loss, rainfall and
-compound hazard share: the checks of sites and groups, the order the kernel wants (the storms of a group next to each other, the
+compound hazard and wind duration share: the checks of sites and groups, the order the kernel wants (the storms of a group next to each other, the
 sites in Z-order), the call, and the way back to the caller's site and storm order."""
 import collections
 import ctypes as C
@@ -42,7 +42,8 @@ def site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, retu
 
     site_extras: further [n_site] inputs (or None), which go through the site permutation with the coordinates.  more_outputs:
     (name, axis) pairs of fp64 outputs along 'trk', 'group' or 'site', or 'pair' for a second [n_site][n_trk] plane like
-    site_max, which come back under their names in the caller's order.  count_cells: the counts of a (site, group) when they are
+    site_max, which come back under their names in the caller's order; an axis ('site_group', k) is an int64
+    [n_site][n_groups][k] output instead.  count_cells: the counts of a (site, group) when they are
     not one per threshold (None: n_bin)."""
     xp = fl.xp
     site_lon, site_lat = (fl.conv(a).reshape(-1) for a in (site_lon, site_lat))
@@ -72,7 +73,8 @@ def site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, retu
     extras = [None if a is None else fl.contiguous(a[site_order]) for a in site_extras]
     counts = fl.new((n_site, n_groups, max(n_bin if count_cells is None else int(count_cells), 1)), 'i4')
     smax = fl.new((n_site, max(n_trk, 1)), 'f8') if return_max else None
-    more = [fl.new((n_site, max(n_trk, 1)) if axis == 'pair' else (max(dict(trk=n_trk, group=n_groups, site=n_site)[axis], 1),), 'f8')
+    more = [fl.new((n_site, n_groups, int(axis[1])), 'i8') if isinstance(axis, tuple) else
+            fl.new((n_site, max(n_trk, 1)) if axis == 'pair' else (max(dict(trk=n_trk, group=n_groups, site=n_site)[axis], 1),), 'f8')
             for _, axis in more_outputs]
     ptr = lambda a: None if a is None else fl.ptr(a)                                      # noqa: E731
     args = make_args(ScanArgs(
@@ -97,7 +99,9 @@ def site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, retu
         return out
     res = dict(counts=by_site(counts), thresholds=thr)
     for (name, axis), a in zip(more_outputs, more):
-        if axis == 'pair':
+        if isinstance(axis, tuple):
+            res[name] = by_site(a)
+        elif axis == 'pair':
             res[name] = by_pair(a)
         elif axis == 'group':
             res[name] = a[:n_groups]
