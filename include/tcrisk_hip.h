@@ -463,6 +463,15 @@ int tcr_probe_rhs_f32_host(tcr_ctx *ctx, int slot, double h_bl, const double *Fs
  * memory.  That decision is taken by rounding in the interior of land, so parity tests compare tracks up
  * to the first evaluation where it lands differently (oracle/parity.py).  Results equal tcr_integrate_host's. */
 int tcr_integrate_probe_host(tcr_ctx *ctx, const tcr_storms *in, const tcr_tracks *out, uint8_t *dec, int32_t cap);
+/* Test instrument of the RK45 step (tests/test_rk_steps.py): tcr_integrate_host / tcr_integrate_f32_host plus the batch's
+ * accepted-step records as the integrator left them, copied before the dense-output kernel rewrites them.  steps is host memory
+ * [n][max_rk_steps][REC] doubles, REC = 36 (fp64) or 20 (fp32), and steps_doubles must be exactly that count (max_rk_steps = 64
+ * when tcr_params.max_rk_steps <= 0).  A record is doubles t_old, h, t_new, one pad; then in the run's type (double, or float
+ * packed two to a double) y_old[4] and the seven stage derivatives K[7][4].  Storm i has min(n_accept[i], max_rk_steps) records;
+ * gated storms have none; what lies behind a storm's last record is stale memory.  Results equal the plain entry point's.
+ * While a call is in progress the _dev entry points and tcr_round_dev on the same context fail. */
+int tcr_integrate_steps_host(tcr_ctx *ctx, const tcr_storms *in, const tcr_tracks *out, double *steps, int64_t steps_doubles);
+int tcr_integrate_steps_f32_host(tcr_ctx *ctx, const tcr_storms *in, const tcr_tracks_f32 *out, double *steps, int64_t steps_doubles);
 /* replaces: gen_f (bam_track.py:23-31): Fs[n][4][n_steps] from phases[n][4][n_series] */
 int tcr_fourier_table_host(tcr_ctx *ctx, int64_t n, const double *phases, double *Fs);
 

@@ -1,7 +1,7 @@
 """The fp32 right-hand side pinned pointwise (tcr_probe_rhs_f32_host, tcr_probe_math_host fn 6-12).
 
-The fp32 variant (tcr_integrate_f32_*, DevicePipeline(dtype='f32'), BASELINE config 5) is otherwise held by distribution statistics
-of whole ensembles; here nothing is integrated (except part E's tie to the shipped kernels), so nothing is amplified:
+Whole fp32 tracks (tcr_integrate_f32_*, DevicePipeline(dtype='f32'), BASELINE config 5) are held by distribution statistics of
+ensembles, the RK45 step by its records (tests/test_rk_steps.py); here the function it integrates: nothing is integrated (except part E's tie to the shipped kernels), so nothing is amplified:
   A  the 20 lookups of an evaluation, bit for bit against tests/rhs_f32_numpy.py (NumPy float32, no fused operation), on every
      static storage mode, on affine and general axes, at the clamps, the end knots, one ulp around knots, in all-land / all-sea cells;
   B  the discrete branches give the oracle's branch and the exact constants;

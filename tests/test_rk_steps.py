@@ -1,0 +1,829 @@
+"""The RK45 step pinned record by record (tcr_integrate_steps_host / _f32_host, TCEngine.integrate(steps=True)).
+
+Every accepted step of k_integrate leaves a record t_old, h, t_new, y_old[4], K[7][4]: a complete statement of one step.  From the
+device's own y_old, K and h everything the step computed is recomputed on the CPU (tests/rk_steps_numpy.py, written from SciPy's
+rk.py / common.py / ivp.py) and compared; nothing is integrated on the reference side, so nothing is amplified:
+  1  the chain of records and the counters, exactly;
+  2  y_new against the long-double value of the same sum, within the forward error bound of seven multiply-adds;
+  3  K[0] of the first record and every K[6] against the single-point probe at their exactly known inputs, bit for bit;
+  4  K[1..5] against the reference right-hand side at the restated stage inputs, in the units of tests/test_rhs_f32.py part C;
+  5  err < 1, the next h from the error norm, the first h from select_initial_step;
+  6  dense output, emission, NaN padding and accept test 1, bit for bit;
+  7  parking / restoring and a short record change nothing.
+The CPU tests prove the restatement (its float64 mode walks scipy.integrate.RK45's steps) and the checker (synthetic float32
+records pass; planted defects of 2^-14 fail) before a GPU sees either.
+"""
+import dataclasses
+import types
+
+import numpy as np
+import pytest
+
+from tests import rhs_f32_numpy as rn
+from tests import rk_steps_numpy as rk
+from tests.test_rhs_f32 import C_BOUNDS, E_YEAR
+
+BASIN = 'GL'
+N_CAND = 256
+STAGE_BOUNDS = np.array([C_BOUNDS[k] for k in ('dlon', 'dlat', 'dv', 'dm')])
+GATED, FINISHED, EVENT, STEP_OVERFLOW = -1, 0, 1, -3
+
+# Measured on the MI355X (test_device_steps prints them), 256 GL candidates of E_YEAR: 162 integrated storms (126 without a rejection),
+# 1 771 records, 7 962 (f32) / 7 963 (f64) of 8 855 stage points kept, at least 1 583 per stage, 24 301 / 24 312 rows.
+#   y_new:  max |y_old[j+1] - y_new_ref| / y_new_bound (check 2; the last rounding alone reaches 0.99)
+#   stages: max normalised error of K[1..5] for dlon, dlat, dv, dm (check 4; bounds C_BOUNDS = 30, 8, 7, 8)
+#   next_h: max distance of h[j+1] from the middle of the allowed interval, in half widths (check 5; the float64 interval is +-2 ulp
+#           of inv_fifth_root wide where err's own bound is small, and one step sits on its end)
+MEASURED = dict(f32=dict(y_new=0.970, stages=(2.52, 1.28, 0.86, 0.99), next_h=0.333),
+                f64=dict(y_new=0.961, stages=(3.07, 2.78, 0.63, 0.82), next_h=1.000))
+
+
+def _prm():
+    from oracle.scipy_port import Params
+    return Params()
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+
+def _same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
+
+
+def event_g(y, bounds):
+    """tc_dissipates (coupled_fast.py:246-256): 0 outside the box shrunk by 1 degree, within 2 degrees of the equator, or v <= 4"""
+    x0, y0, x1, y1 = bounds
+    inside = (y[0] >= x0 + 1) and (y[0] <= x1 - 1) and (y[1] >= y0 + 1) and (y[1] <= y1 - 1)
+    if not inside or abs(y[1]) <= 2:
+        return 0.0
+    return max(0.0, float(y[2]) - 4.0)
+
+
+# ------------------------------------------------------------------------------------------------ the reference right-hand side
+class OracleRhs:
+    """The C oracle as the right-hand side of storm i of a batch: on the float-rounded data (R = float32: rhs_f32_numpy.env_f32 /
+    params_f32, the table and h_bl rounded to float) or on the data as they are (float64).  Also the yardsticks of check 4."""
+
+    def __init__(self, env, storms, R):
+        from oracle import c_oracle
+        self.R, self.storms = R, storms
+        self.f32 = R == np.float32
+        self.env = rn.env_f32(env) if self.f32 else env
+        self.prm = rn.params_f32(_prm()) if self.f32 else _prm()
+        self._cme, self._L64, self._Fs = {}, {}, {}
+        self.c_oracle = c_oracle
+
+    def cme(self, i):
+        mo = int(self.storms['month'][i]) - 1
+        if mo not in self._cme:
+            self._cme[mo] = self.c_oracle.CMonthEnv(self.env, BASIN, mo)
+        return self._cme[mo]
+
+    def L64(self, i):
+        mo = int(self.storms['month'][i]) - 1
+        if mo not in self._L64:
+            self._L64[mo] = rn.Lookups(self.env, BASIN, mo, np.float64)
+        return self._L64[mo]
+
+    def Fs(self, i):
+        if i not in self._Fs:
+            Fs = self.c_oracle.fourier_table(self.storms['phases'][i])
+            self._Fs[i] = rn.f32(Fs) if self.f32 else Fs
+        return self._Fs[i]
+
+    def h_bl(self, i):
+        return float(self.R(self.storms['h_bl'][i]))
+
+    def outputs(self, i, t, y):
+        y = np.asarray(y, np.float64)
+        with np.errstate(all='ignore'):
+            return rn.oracle_outputs(self.cme(i), self.prm, self.Fs(i), self.h_bl(i), np.asarray(t, np.float64), y[:, 0], y[:, 1], y[:, 2], y[:, 3])
+
+    def __call__(self, i, t, y):
+        """dydt [N, 4] in R at times t [N] and states y [N, 4]"""
+        return self.outputs(i, t, y)[:, :4].astype(self.R)
+
+    def twin(self, i, t, y, ref):
+        """the oracle's response to one ulp of R in each of lon, lat, v, m, up and down (rhs_f32_numpy.twin_response; in float64 mode
+        the same with float64 neighbours)"""
+        y = np.asarray(y, np.float64)
+        if self.f32:
+            with np.errstate(all='ignore'):
+                return rn.twin_response(self.cme(i), self.prm, self.Fs(i), self.h_bl(i), np.asarray(t, np.float64), y[:, 0], y[:, 1], y[:, 2], y[:, 3], ref)
+        tw = np.zeros_like(ref)
+        for c in range(4):
+            for sgn in (np.inf, -np.inf):
+                yp = y.copy()
+                yp[:, c] = np.nextafter(y[:, c], sgn)
+                tw = np.fmax(tw, np.abs(self.outputs(i, t, yp) - ref))
+        return tw
+
+    def mag(self, i, t, y, ref):
+        y = np.asarray(y, np.float64)
+        with np.errstate(all='ignore'):
+            return rn.magnitudes(self.L64(i), self.prm, self.Fs(i), self.h_bl(i), np.asarray(t, np.float64), y[:, 0], y[:, 1], y[:, 2], y[:, 3], ref)
+
+    def keep(self, i, y):
+        y = np.asarray(y, np.float64)
+        return rn.select_continuous(self.L64(i), y[:, 0], y[:, 1])[0]
+
+
+# ------------------------------------------------------------------------------------------------ the checks (no GPU in them)
+# A batch is a dict: 'R'; 'storms' (lon, lat, v0, m0, h_bl, month, phases); 'status', 'n_valid', 'nfev', 'n_accept', 'n_reject',
+# 'steps_n' [n]; 'rec' (a list of rk.Records, storm i's first steps_n[i] records); rows 'lon', 'lat', 'v', 'm' [n, n_steps] and
+# 'is_tc' [n] where check 6 is run.  prm: total_time, n_steps, rtol, atol, max_step, v_thresh, v_2d_thresh.
+
+def integrated(b):
+    return np.flatnonzero(b['status'] != GATED)
+
+
+def seeds_R(b, i):
+    s = b['storms']
+    return np.array([s['lon'][i], s['lat'][i], s['v0'][i], s['m0'][i]], np.float64).astype(b['R'])
+
+
+def check_chain(b, prm, max_rk):
+    """1.  Exact."""
+    for i in range(len(b['status'])):
+        r, n = b['rec'][i], int(b['steps_n'][i])
+        if b['status'][i] == GATED:
+            assert b['nfev'][i] == 0 and n == 0 and b['n_valid'][i] == 0, i
+            continue
+        assert n == min(int(b['n_accept'][i]), max_rk) and n >= 1 and len(r) == n, i
+        assert b['nfev'][i] == 2 + 6 * (int(b['n_accept'][i]) + int(b['n_reject'][i])), i
+        assert r.t_old[0] == 0 and (r.h > 0).all(), i
+        assert np.array_equal(r.t_new[:-1], r.t_old[1:]), i
+        plain = r.t_new == r.t_old + r.h
+        clipped = (r.t_new == prm.total_time) & (r.h == prm.total_time - r.t_old)
+        assert (plain | clipped).all(), (i, np.flatnonzero(~(plain | clipped)))
+        assert _same(r.y[0], seeds_R(b, i)), i
+        assert _same(r.K[:-1, 6], r.K[1:, 0]), i
+        if n == int(b['n_accept'][i]):
+            # solve_ivp's status is 0 at t_bound unless the terminal event fires at that very step's end (ivp.py:660-693: status 1)
+            if r.t_new[-1] >= prm.total_time and b['status'][i] != FINISHED:
+                from oracle.scipy_port import BASIN_BOUNDS
+                last = r[slice(n - 1, n)]
+                assert b['status'][i] == EVENT and any(event_g(rk.y_new_variant(last, f)[0], BASIN_BOUNDS[BASIN]) == 0 for f in (True, False)), i
+            else:
+                assert (b['status'][i] == FINISHED) == bool(r.t_new[-1] >= prm.total_time), i
+        else:
+            assert b['status'][i] == STEP_OVERFLOW, i
+
+
+def pairs(b):
+    """All records that have a successor, and the successors: (Records, Records, storm index per pair)"""
+    cur, nxt, who = [], [], []
+    for i in integrated(b):
+        r = b['rec'][i]
+        if len(r) > 1:
+            cur.append(r[slice(0, len(r) - 1)]); nxt.append(r[slice(1, len(r))]); who.append(np.full(len(r) - 1, i))
+    return rk.Records.concat(cur), rk.Records.concat(nxt), np.concatenate(who)
+
+
+# The form the compiler emitted for k_integrate<float> under TCR_FP_FUSE_RK, read from its assembly and confirmed by check 2: the sums
+# of the lon and lat components (formed before the intensity half of the evaluation) are packed multiplies followed by separate adds,
+# those of v and m (formed after it) are fused multiply-adds; the last operation, y + h * dy, is fused for all four.  k_integrate<double>
+# is fused throughout.  The stage times t + C_s h, float64 in both, are fused multiply-adds in both.
+# (sum per component, last operation, stage time)
+DEVICE_FORM = dict(f32=((False, False, True, True), True, True), f64=(True, True, True))
+
+
+def check_y_new(b, tab=None):
+    """2.  |y_old[j+1] - y_new_ref(rec_j)| / y_new_bound per pair and component, and the share of pairs each all-or-nothing form
+    reproduces bit for bit."""
+    cur, nxt, _ = pairs(b)
+    ratio = np.abs(nxt.y.astype(rk.LD) - rk.y_new_ref(cur, tab)).astype(np.float64) / rk.y_new_bound(cur, tab)
+    share = {f: float((_bits(rk.y_new_variant(cur, f, tab)) == _bits(nxt.y)).all(axis=1).mean()) for f in (True, False)}
+    # the two mixed forms: (sum fused, last operation separate), (sum separate, last operation fused)
+    form = DEVICE_FORM['f32' if b['R'] == np.float32 else 'f64']
+    share['device'] = float((_bits(rk.y_new_variant(cur, form[0], tab, fused_last=form[1])) == _bits(nxt.y)).all(axis=1).mean())
+    share['mixed'] = tuple(float((_bits(rk.y_new_variant(cur, f, tab, fused_last=not f)) == _bits(nxt.y)).all(axis=1).mean()) for f in (True, False))
+    return ratio, share
+
+
+def endpoint_points(b, i):
+    """3.  The evaluations whose inputs are exactly known: K[0] of record 0 at (0, y0), K[6] of record j at (t_new[j], y_old[j+1])."""
+    r = b['rec'][i]
+    t = np.concatenate([[0.0], r.t_new[:-1]])
+    y = np.concatenate([r.y[:1], r.y[1:]])
+    want = np.concatenate([r.K[:1, 0], r.K[:-1, 6]])
+    return t, y, want
+
+
+def check_endpoints(b, rhs):
+    bad = total = 0
+    for i in integrated(b):
+        t, y, want = endpoint_points(b, i)
+        got = rhs(i, t, y)
+        bad += int((_bits(got) != _bits(want)).any(axis=1).sum())
+        total += len(t)
+    return bad, total
+
+
+def stage_points(b, i, tab=None, fused=False, fused_last=None, fused_time=False):
+    """the five intermediate stage points of every record of storm i: t [N, 5], y [N, 5, 4]"""
+    r = b['rec'][i]
+    t = np.stack([rk.stage_time(r, s, tab, fused_time) for s in range(1, 6)], axis=1)
+    y = np.stack([rk.stage_input(r, s, fused, tab, fused_last) for s in range(1, 6)], axis=1)
+    return t, y
+
+
+class StageReference:
+    """4.  Per storm, computed once: the oracle's derivative at the unfused stage inputs, its twin response and the magnitudes, and
+    which points rhs_f32_numpy.select_continuous keeps."""
+
+    def __init__(self, b, orc):
+        self.b, self.orc, self.per = b, orc, {}
+        for i in integrated(b):
+            t, y = stage_points(b, i)
+            tf, yf = t.reshape(-1), y.reshape(-1, 4)
+            ref = orc.outputs(i, tf, yf)
+            self.per[i] = dict(ref=ref, twin=orc.twin(i, tf, yf, ref), mag=orc.mag(i, tf, yf, ref), keep=orc.keep(i, yf), shape=t.shape)
+
+    def errors(self, got_of):
+        """got_of(i) -> [N, 5, 4] derivatives to judge.  Returns the normalised errors [M, 4] of the kept points, their stage index
+        [M], and the numbers of kept and of all points."""
+        u = rk.unit_roundoff(self.b['R'])
+        es, ss, kept, total = [], [], 0, 0
+        for i, p in self.per.items():
+            n = p['shape'][0]
+            s = np.tile(np.arange(1, 6), n)
+            got = np.asarray(got_of(i), np.float64).reshape(-1, 4)
+            count = (1 + s + 2)[:, None]                      # roundings by which a fused and an unfused stage input can differ, + 1
+            with np.errstate(all='ignore'):
+                e = np.abs(got - p['ref'][:, :4]) / (count * p['twin'][:, :4] + u * p['mag'][:, :4])
+            k = p['keep']
+            es.append(e[k]); ss.append(s[k]); kept += int(k.sum()); total += k.size
+        return np.concatenate(es), np.concatenate(ss), kept, total
+
+
+def check_controller(b, prm, tab=None):
+    """5.  Returns per pair: whether h[j+1] lies in the interval the restated controller allows (== for storms without a rejection,
+    upper end only otherwise), the distance from the interval's middle in units of its half width, and err - 1 - bound per record."""
+    tab = tab or rk.Tableau(b['R'])
+    cur, nxt, who = pairs(b)
+    f_lo, f_hi, e, eb = rk.factor_interval(cur, nxt.y, prm.rtol, prm.atol, tab)
+    # the float64 operations of rk.py:127-146 themselves, each monotone: an interval goes through as one
+    h_lo = rk.clipped_step(cur.t_new, cur.h * f_lo, prm.total_time, prm.max_step)[0]
+    h_hi = rk.clipped_step(cur.t_new, cur.h * f_hi, prm.total_time, prm.max_step)[0]
+    clean = (b['n_reject'][who] == 0)
+    ok = (nxt.h <= h_hi) & (~clean | (nxt.h >= h_lo))
+    mid, half = 0.5 * (h_lo + h_hi), np.maximum(0.5 * (h_hi - h_lo), np.spacing(h_hi))
+    dist = np.where(clean, np.abs(nxt.h - mid) / half, np.maximum(nxt.h - mid, 0) / half)
+    return ok, dist, e - 1 - eb, clean
+
+
+def check_last_err(b, prm, tab=None):
+    """5.  err < 1 + bound for the last record of every storm, whose y_new has no successor: with either all-or-nothing y_new"""
+    last = rk.Records.concat([b['rec'][i][slice(len(b['rec'][i]) - 1, len(b['rec'][i]))] for i in integrated(b)])
+    ok = np.zeros(len(last), bool)
+    for f in (True, False):
+        yn = rk.y_new_variant(last, f, tab)
+        ok |= rk.err(last, yn, prm.rtol, prm.atol, tab) < 1 + rk.err_abs_bound(last, yn, prm.rtol, prm.atol, tab)
+    return ok
+
+
+def check_first_step(b, prm, rhs):
+    """5.  h[0] <= min(100 h0, total_time, max_step) for every storm; for storms without a rejection h[0] equals select_initial_step's
+    value to 1e-12, with f1 at the fused or the unfused y0 + h0 f0.  Returns the relative deviations of the latter."""
+    dev = []
+    for i in integrated(b):
+        r = b['rec'][i]
+        y0, f0 = r.y[:1], r.K[:1, 0]
+        h0 = rk.initial_h0(y0, f0, prm.rtol, prm.atol, prm.total_time)
+        assert r.h[0] <= min(100 * h0[0], prm.total_time, prm.max_step), i
+        if b['n_reject'][i] == 0:
+            best = np.inf
+            for f in (True, False):
+                y1 = rk.initial_y1(y0, f0, h0, f)
+                f1 = rhs(i, h0, y1)
+                want = rk.clipped_step(0.0, rk.initial_h(y0, f0, f1, h0, prm.rtol, prm.atol, prm.total_time, prm.max_step), prm.total_time, prm.max_step)[0]
+                best = min(best, abs(r.h[0] / want[0] - 1))
+            dev.append(best)
+    return np.array(dev)
+
+
+def expected_n_valid(b, i, grid):
+    r = b['rec'][i]
+    t_emit = r.t_new[-1]
+    if b['status'][i] == EVENT and len(r) == 1 and b['n_accept'][i] == 1:
+        from oracle.scipy_port import BASIN_BOUNDS
+        if event_g(r.y[0], BASIN_BOUNDS[BASIN]) == 0:                 # the event function is 0 at t0: the root is the step's start (ivp.py:673-693)
+            t_emit = r.t_old[0]
+    return int(grid.samples_upto(t_emit))
+
+
+def check_dense(b, prm, tab=None, planes=None):
+    """6.  Bit for bit.  Returns the number of rows compared."""
+    grid = rk.Grid(prm.total_time, prm.n_steps)
+    R, rows_seen = b['R'], 0
+    for i in range(len(b['status'])):
+        nv = int(b['n_valid'][i])
+        for k in planes or ('lon', 'lat', 'v', 'm'):
+            assert np.isnan(b[k][i, nv:]).all(), (i, k)
+        if b['status'][i] == GATED:
+            assert nv == 0 and not b['is_tc'][i], i
+            continue
+        assert nv == expected_n_valid(b, i, grid), (i, nv)
+        rows, owner = rk.storm_rows(b['rec'][i], grid, nv, tab)
+        assert (owner >= 0).all(), i
+        got = np.stack([b[k][i, :nv] for k in ('lon', 'lat', 'v', 'm')], axis=1)
+        assert got.dtype == R and _same(got, rows), (i, np.flatnonzero((_bits(got) != _bits(rows)).any(axis=1))[:4])
+        assert _same(got[0], seeds_R(b, i)), i
+        assert bool(b['is_tc'][i]) == rk.is_tc(got[:, 2], grid, prm.v_thresh, prm.v_2d_thresh), i
+        rows_seen += nv
+    return rows_seen
+
+
+# ------------------------------------------------------------------------------------------------ CPU tests
+def _toy(t, y):
+    """a smooth 4-component system on the scales of a track (degrees, m/s, a fraction; seconds)"""
+    lon, lat, v, m = (float(x) for x in y)
+    return np.array([4e-5 * np.cos(t / 5e4) * (1 + v / 40.0), 2e-5 * np.sin(lon / 7.0) + 1e-5,
+                     3e-5 * (45.0 * m - v) - 1e-6 * v * np.sin(t / 2.3e4), 4e-6 * (1 - m) * v / 10.0 - 2e-6 * m * (1 + np.cos(lat / 3.0))])
+
+
+def _against_scipy(fun, y0, prm, max_accept):
+    """scipy.integrate.RK45 walked step by step; every step is restated (float64, unfused) from SciPy's own state before it — t, y,
+    f, the proposed h — so that one step is compared with one step.  (A free run of the restatement is compared as well, for the
+    sequence of accepts and rejects: its t drifts from SciPy's by 2e-13 within five steps of the smooth toy system, because the
+    error norm is a cancelling sum whose last bits depend on the order in which np.dot adds — which varies with the alignment of
+    SciPy's arrays from run to run — and h follows err^-0.2.)  Per step: the same number of rejected attempts, t and h to 1e-13,
+    y_new and K to 1e-12, the dense output on the hourly samples of the step to 1e-12, and SciPy's next proposal inside the
+    interval check 5 allows around the restated one (rk.factor_interval on SciPy's own K)."""
+    from scipy.integrate import RK45
+    grid = rk.Grid(prm.total_time, prm.n_steps)
+    args = (prm.total_time, np.float64, False, prm.rtol, prm.atol, prm.max_step)
+    sol = RK45(fun, 0.0, np.asarray(y0, np.float64), prm.total_time, max_step=prm.max_step, rtol=prm.rtol, atol=prm.atol)
+    f0, h_abs, _, _, _ = rk.first_step(fun, y0, *args)
+    assert np.array_equal(f0, sol.f) and abs(h_abs / sol.h_abs - 1) <= 1e-13
+    free = rk.run(fun, y0, *args, max_accept=max_accept)
+    free_rejects, k = [], 0
+    for acc, _, _ in free['log']:
+        if acc:
+            free_rejects.append(k); k = 0
+        else:
+            k += 1
+    steps = rejects = samples = 0
+    drift = 0.0
+    while sol.status == 'running' and steps < max_accept:
+        t0, y0_, f0, h_in, nfev0 = sol.t, sol.y.copy(), sol.f.copy(), sol.h_abs, sol.nfev
+        assert sol.step() is None and sol.status in ('running', 'finished')
+        one, yn, h_next, log = rk.step(fun, t0, y0_, f0, h_in, *args)
+        n_rej = (sol.nfev - nfev0) // 6 - 1
+        assert n_rej == len(log) - 1 and n_rej == free_rejects[steps], (steps, 'accept / reject sequence')
+        assert abs(sol.t - one.t_new[0]) <= 1e-13 * sol.t and abs((sol.t - sol.t_old) - one.h[0]) <= 1e-13 * one.h[0], steps
+        assert np.allclose(yn, sol.y, rtol=1e-12, atol=0), steps
+        scale = np.abs(sol.K).max(axis=0)
+        assert np.allclose(one.K[0], sol.K, rtol=1e-12, atol=1e-12 * scale.max()), steps
+        own = rk.Records([sol.t_old], [sol.t - sol.t_old], [sol.t], y0_[None], sol.K[None].copy())
+        f_lo, f_hi, _, _ = rk.factor_interval(own, sol.y[None], prm.rtol, prm.atol)
+        if n_rej == 0:
+            assert own.h[0] * f_lo[0] <= sol.h_abs <= own.h[0] * f_hi[0], (steps, own.h[0] * f_lo[0], sol.h_abs, own.h[0] * f_hi[0])
+        else:
+            assert sol.h_abs <= own.h[0] * f_hi[0], steps
+        lo, hi = (0 if steps == 0 else grid.samples_upto(sol.t_old)), grid.samples_upto(sol.t)
+        if hi > lo:
+            ts = grid.ts[lo:hi]
+            want = sol.dense_output()(ts).T
+            got = rk.dense_eval(one, rk.dense_rows(one), np.zeros(hi - lo, int), ts)
+            assert np.allclose(got, want, rtol=1e-12, atol=1e-12 * np.abs(want).max()), steps
+            samples += hi - lo
+        drift = max(drift, abs(free['rec'].t_new[steps] / sol.t - 1))
+        steps += 1; rejects += n_rej
+    assert steps == len(free['rec']) and (sol.status == 'finished') == (free['status'] == 'finished')
+    assert drift <= 1e-9, drift
+    return steps, rejects, samples, drift
+
+
+def _oracle_storms(env, n_cand, year=E_YEAR):
+    from oracle import seeding
+    from tropical_cyclone_risk_amd import namelist
+    s = seeding.seed_candidates(seeding.SeedEnv(env, BASIN), namelist.gpu_experiment_seed, year, 0, n_cand)
+    return {k: s[k] for k in ('lon', 'lat', 'v0', 'm0', 'h_bl', 'month', 'phases')}
+
+
+def _not_gated(env, storms):
+    from oracle import c_oracle
+    return np.flatnonzero(c_oracle.run_ensemble(env, BASIN, storms, post=False)['status'] != GATED)
+
+
+def test_restatement_walks_scipy_rk45(golden_env):
+    """The stepper built from the restatement, float64 and unfused, against scipy.integrate.RK45 with the namelist's rtol / atol /
+    max_step (_against_scipy): the same accepts and rejects, t and h to 1e-13, y to 1e-12, dense output on the hourly grid to
+    1e-12 — on a smooth toy system over the whole 15 days, and on 8 seeded storms driven by the C oracle's right-hand side (12
+    accepted steps each)."""
+    prm = _prm()
+    n, rej, smp, drift = _against_scipy(_toy, [300.0, 15.0, 8.0, 0.3], prm, 200)
+    print('toy: %d steps, %d rejected attempts, %d samples; the free run drifts by %.1e' % (n, rej, smp, drift))
+    assert n >= 15 and smp == prm.n_steps
+    storms = _oracle_storms(golden_env, 32)
+    orc = OracleRhs(golden_env, storms, np.float64)
+    tot, drift = np.zeros(3, int), 0.0
+    for i in _not_gated(golden_env, storms)[:8]:
+        fun = lambda t, y, i=i: orc(i, [t], np.asarray(y)[None])[0]
+        out = _against_scipy(fun, seeds_R(dict(storms=storms, R=np.float64), i), prm, 12)
+        tot += out[:3]; drift = max(drift, out[3])
+    print('8 storms: %d steps, %d rejected attempts, %d samples; the free run drifts by %.1e' % (tuple(tot) + (drift,)))
+    assert tot[0] >= 60 and tot[2] >= 200
+
+
+def test_fma_emulation_is_exact():
+    """rk.fma in float32 against exact rational arithmetic, ties included: operands built so that a * b + c lies exactly half way
+    between two floats, and a hair to either side of it."""
+    from fractions import Fraction as Fr
+    R = np.float32
+    rng = np.random.default_rng(3)
+    a = rng.uniform(0.5, 2, 4000).astype(R) * rng.choice([-1, 1], 4000).astype(R)
+    b = rng.uniform(0.5, 2, 4000).astype(R)
+    c = (rng.normal(size=4000) * 10.0 ** rng.uniform(-9, 2, 4000)).astype(R)
+    # a * b = 2^-17 - 2^-63: half an ulp of a float c in [128, 256), less a hair that the double sum c + a * b cannot hold.  The
+    # double sum is then the exact tie, and rounding IT to float goes to the even neighbour whichever side the hair is on
+    a[:2000], b[:2000] = R(2.0 ** -17) * (R(1) + R(2.0 ** -23)), R(1) - R(2.0 ** -23)
+    c[:2000] = rng.uniform(128, 256, 2000).astype(R) * rng.choice([-1, 1], 2000).astype(R)
+    got = rk.fma(a, b, c, R)
+
+    def exact(x, y, z):
+        v = Fr(float(x)) * Fr(float(y)) + Fr(float(z))
+        lo = R(float(v))
+        cand = sorted({lo, np.nextafter(lo, R(np.inf)), np.nextafter(lo, R(-np.inf))}, key=float)
+        best = min(cand, key=lambda f: (abs(Fr(float(f)) - v), int(np.array(f, R).view(np.uint32)) & 1))
+        return best
+    want = np.array([exact(x, y, z) for x, y, z in zip(a, b, c)], R)
+    assert np.array_equal(_bits(got), _bits(want)), int((_bits(got) != _bits(want)).sum())
+    twice = (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(R)
+    # float64: rational arithmetic by construction; (1 + 2^-30)(1 - 2^-30) - 1 = -2^-60 exactly, 0 when the product is rounded first
+    x = np.array([1 + 2.0 ** -30])
+    assert rk.fma(x, 1 - 2.0 ** -30, -1.0, np.float64)[0] == -2.0 ** -60 and x[0] * (1 - 2.0 ** -30) - 1.0 == 0.0
+    n_twice = int((_bits(twice) != _bits(got)).sum())
+    print('fma: %d operands, %d of them differ from rounding through double' % (a.size, n_twice))
+    assert n_twice >= 500
+
+
+def synthetic_batch(env, storms, idx, fused, prm):
+    """Records of the float32 stepper (every multiply-add fused, or none) on storms idx, the oracle on the float-rounded data as
+    the right-hand side, with the counters, rows and flags a device batch has."""
+    from oracle.scipy_port import BASIN_BOUNDS
+    R = np.float32
+    sub = {k: np.asarray(v)[idx] for k, v in storms.items()}
+    orc = OracleRhs(env, sub, R)
+    grid = rk.Grid(prm.total_time, prm.n_steps)
+    n = len(idx)
+    b = dict(R=R, storms=sub, rec=[], status=np.zeros(n, np.int32), n_valid=np.zeros(n, np.int32), nfev=np.zeros(n, np.int32),
+             n_accept=np.zeros(n, np.int32), n_reject=np.zeros(n, np.int32), steps_n=np.zeros(n, np.int32), is_tc=np.zeros(n, bool))
+    for k in ('lon', 'lat', 'v', 'm'):
+        b[k] = np.full((n, prm.n_steps), np.nan, R)
+    for i in range(n):
+        calls = [0]
+
+        def fun(t, y, i=i, calls=calls):
+            calls[0] += 1
+            return orc(i, [t], np.asarray(y)[None])[0]
+        y0 = seeds_R(b, i)
+        g0 = event_g(y0, BASIN_BOUNDS[BASIN])
+        out = rk.run(fun, y0, prm.total_time, R, fused, prm.rtol, prm.atol, prm.max_step, max_accept=64,
+                     stop=lambda t, y: g0 == 0 or event_g(y, BASIN_BOUNDS[BASIN]) == 0)
+        r = out['rec']
+        b['rec'].append(r)
+        b['status'][i] = FINISHED if out['status'] == 'finished' else EVENT
+        assert out['status'] in ('finished', 'stopped')
+        b['nfev'][i] = calls[0]
+        b['n_accept'][i] = b['steps_n'][i] = len(r)
+        b['n_reject'][i] = sum(1 for a, _, _ in out['log'] if not a)
+        nv = expected_n_valid(b, i, grid)
+        b['n_valid'][i] = nv
+        rows, _ = rk.storm_rows(r, grid, nv)
+        for c, k in enumerate(('lon', 'lat', 'v', 'm')):
+            b[k][i, :nv] = rows[:, c]
+        b['is_tc'][i] = rk.is_tc(rows[:, 2], grid, prm.v_thresh, prm.v_2d_thresh)
+    return b, orc
+
+
+# the exponent of the planted relative defect each class of coefficient needs to fail its check on >= 1 % of the steps
+PLANT_EXP = dict(A20=-13, A43=-13, A53=-13)            # every other one: -14
+
+
+def test_checker_on_synthetic_records(golden_env):
+    """The checker without a GPU.  The float32 stepper of the restatement runs 32 seeded storms twice, every multiply-add fused and
+    none fused, with the C oracle on the float-rounded data as the right-hand side; both record sets pass checks 1, 2, 3 (the oracle
+    in the probe's place), 4, 5 and 6.  Then ONE relative defect is planted in the checker's tableau — against correct records the
+    mirror image, to first order, of the same defect in the code that wrote them, and the only form that needs no re-integration —
+    and its own check must fail on at least 1 % of the steps:
+      every nonzero A[s][j]   -> check 4 at stage s (K[s] as evaluated at the defective stage input)
+      every C[s], s = 1..5    -> check 4 at stage s (the stage time moves)
+      every nonzero B[j]      -> check 2
+      every nonzero E[j], and the error scale from |y| alone -> check 5 through the next h
+      every nonzero column of P -> check 6
+    The exponent starts at 2^-14 and is raised by powers of two until the defect is seen; none above 2^-8 is accepted.
+    Needed (the test prints each one with the share of steps that fail): 2^-14 for every B, E, C and column of P, for the scale and
+    for twelve of the fifteen A; 2^-13 for A20, A43 and A53, the three smallest contributions to their stage inputs (PLANT_EXP)."""
+    prm = _prm()
+    storms = _oracle_storms(golden_env, 64)
+    idx = _not_gated(golden_env, storms)[:32]
+    assert len(idx) == 32
+    batches = {}
+    for fused in (True, False):
+        b, orc = synthetic_batch(golden_env, storms, idx, fused, prm)
+        batches[fused] = (b, orc)
+        nrec = int(b['steps_n'].sum())
+        check_chain(b, prm, 64)
+        ratio, share = check_y_new(b)
+        assert ratio.max() <= 1.0, ratio.max()
+        assert share[fused] == 1.0
+        bad, total = check_endpoints(b, orc)
+        assert bad == 0 and total == nrec
+        sr = StageReference(b, orc)
+        e, s, kept, total = sr.errors(lambda i: b['rec'][i].K[:, 1:6])
+        assert kept >= 0.5 * total and (e <= STAGE_BOUNDS).all(), (kept, total, e.max(axis=0))
+        ok, dist, over, clean = check_controller(b, prm)
+        assert ok.all() and (over < 0).all() and check_last_err(b, prm).all()
+        dev = check_first_step(b, prm, orc)
+        assert len(dev) >= 10 and dev.max() <= 1e-12
+        rows = check_dense(b, prm)
+        print('synthetic %s: %d storms (%d without a rejection), %d records, %d rows; y_new within %.2f of its bound, reproduced bit for bit '
+              'by fused %.3f / unfused %.3f; stage points kept %d of %d, max normalised error %s'
+              % ('fused' if fused else 'unfused', len(idx), int((b['n_reject'] == 0).sum()), nrec, rows, ratio.max(), share[True], share[False],
+                 kept, total, np.round(e.max(axis=0), 2)))
+        batches[fused] += (sr,)
+
+    def seen(what, index, check):
+        """the smallest exponent >= PLANT_EXP's at which `check(tab)` fails on >= 1 % of the steps, on both record sets"""
+        for ex in range(-14, -7):
+            shares = [check(batches[f], rk.Tableau(np.float32).planted(what, index, 2.0 ** ex)) for f in (True, False)]
+            if min(shares) >= 0.01:
+                return ex, min(shares)
+        raise AssertionError('defect in %s%s not seen at 2^-8: %s' % (what, index, shares))
+
+    def stage_check(s):
+        def check(bo, tab):
+            b, orc, sr = bo
+            def got(i):
+                t, y = stage_points(b, i, tab)
+                K = b['rec'][i].K[:, 1:6].astype(np.float64).copy()
+                K[:, s - 1] = orc.outputs(i, t[:, s - 1], y[:, s - 1])[:, :4]
+                return K
+            e, st, _, _ = sr.errors(got)
+            return float((e[st == s] > STAGE_BOUNDS).any(axis=1).mean())
+        return check
+
+    def y_check(bo, tab):
+        ratio, _ = check_y_new(bo[0], tab)
+        return float((ratio > 1).any(axis=1).mean())
+
+    def h_check(bo, tab):
+        ok, _, _, clean = check_controller(bo[0], prm, tab)
+        return float((~ok).mean())
+
+    def dense_check(bo, tab):
+        b = bo[0]
+        grid = rk.Grid(prm.total_time, prm.n_steps)
+        bad = tot = 0
+        for i in range(len(b['status'])):
+            nv = int(b['n_valid'][i])
+            rows, owner = rk.storm_rows(b['rec'][i], grid, nv, tab)
+            got = np.stack([b[k][i, :nv] for k in ('lon', 'lat', 'v', 'm')], axis=1)
+            wrong = (_bits(got) != _bits(rows)).any(axis=1)
+            bad += len(np.unique(owner[wrong])); tot += len(b['rec'][i])
+        return bad / tot
+
+    found = {}
+    for s in range(1, 6):
+        for j in range(s):
+            found['A%d%d' % (s, j)] = seen('A', (s, j), stage_check(s))
+        found['C%d' % s] = seen('C', s, stage_check(s))
+    for j in (0, 2, 3, 4, 5):
+        found['B%d' % j] = seen('B', j, y_check)
+    for j in (0, 2, 3, 4, 5, 6):
+        found['E%d' % j] = seen('E', j, h_check)
+    found['sc'] = seen('sc', None, h_check)
+    for k in (1, 2, 3):
+        found['P.%d' % k] = seen('P', k, dense_check)
+    found['P.0'] = seen('P', 0, dense_check)
+    print('planted defects: exponent needed, share of steps failing')
+    for k, (ex, share) in found.items():
+        print('  %-4s 2^%d  %.3f' % (k, ex, share))
+        assert share >= 0.01 and ex <= -8 and ex <= PLANT_EXP.get(k, -14), (k, ex, share)
+    # a dense-output term with the wrong power
+    b = batches[False][0]
+    grid = rk.Grid(prm.total_time, prm.n_steps)
+    r = b['rec'][0]
+    nv = int(b['n_valid'][0])
+    rows, owner = rk.storm_rows(r, grid, nv)
+    wrong = rk.dense_eval(r, rk.dense_rows(r), owner, grid.ts[:nv], powers=(1, 2, 3, 3))
+    assert (_bits(wrong) != _bits(rows)).any(axis=1).mean() > 0.5
+
+
+def test_device_batch_meets_its_conditions_by_the_oracle(golden_env):
+    """What test_device_steps needs of its batch — the first 256 GL candidates of E_YEAR — counted with the C oracle alone (the
+    oracle's seeding is the device's, tests/test_seeding.py): at least 80 integrated storms, 30 without a rejection, 1 500 accepted
+    steps, one storm ending by event and one at t_bound, and rhs_f32_numpy.select_continuous keeping at least half of the hourly
+    track points.  Counted: 162 integrated, 126 without a rejection, 1 771 steps, 140 events, 22 at t_bound, 86 % kept."""
+    from oracle import c_oracle
+    storms = _oracle_storms(golden_env, N_CAND)
+    ref = c_oracle.run_ensemble(golden_env, BASIN, storms, post=False)
+    on = ref['status'] != GATED
+    assert on.sum() >= 80 and (on & (ref['n_reject'] == 0)).sum() >= 30 and ref['n_accept'][on].sum() >= 1500
+    assert (ref['status'] == EVENT).any() and (ref['status'] == FINISHED).any()
+    orc = OracleRhs(golden_env, storms, np.float32)
+    kept = total = 0
+    for i in np.flatnonzero(on):
+        nv = int(ref['n_valid'][i])
+        kept += int(orc.keep(i, rn.f32(ref['traj'][i, :, :nv].T)).sum()); total += nv
+    print('%d integrated, %d without a rejection, %d steps, %d events, %d at t_bound, %.0f %% of %d track points kept'
+          % (on.sum(), (on & (ref['n_reject'] == 0)).sum(), ref['n_accept'][on].sum(), (ref['status'] == EVENT).sum(), (ref['status'] == FINISHED).sum(),
+             100.0 * kept / total, total))
+    assert kept >= 0.5 * total
+
+
+# ------------------------------------------------------------------------------------------------ GPU tests
+def _engine(env, max_rk=None):
+    from tropical_cyclone_risk_amd import namelist
+    from tropical_cyclone_risk_amd.engine import TCEngine
+    nl = types.SimpleNamespace(**{k: getattr(namelist, k) for k in dir(namelist) if not k.startswith('__')})
+    if max_rk:
+        nl.gpu_max_rk_steps = max_rk
+    return TCEngine(BASIN, device=0, nl=nl).stage_env(env)
+
+
+def device_batch(eng, storms, dtype, out=None):
+    out = out if out is not None else eng.integrate(storms, dtype=dtype, steps=True)
+    R = np.float32 if dtype == 'f32' else np.float64
+    n = len(out['status'])
+    assert out['steps_y'].dtype == R and out['steps_K'].dtype == R and out['lon'].dtype == R
+    b = dict(R=R, storms=storms, rec=[])
+    for k in ('status', 'n_valid', 'nfev', 'n_accept', 'n_reject', 'steps_n', 'is_tc', 'lon', 'lat', 'v', 'm', 'vmax', 'envw'):
+        b[k] = out[k]
+    for i in range(n):
+        m = int(out['steps_n'][i])
+        b['rec'].append(rk.Records(out['steps_t_old'][i, :m], out['steps_h'][i, :m], out['steps_t_new'][i, :m], out['steps_y'][i, :m], out['steps_K'][i, :m]))
+    return b
+
+
+STEP_KEYS = ('steps_t_old', 'steps_h', 'steps_t_new', 'steps_y', 'steps_K')
+COUNTERS = ('status', 'n_valid', 'nfev', 'n_accept', 'n_reject', 'steps_n', 'flags')
+
+
+def _records_equal(a, b, i, m):
+    return all(_same(a[k][i, :m], b[k][i, :m]) for k in STEP_KEYS)
+
+
+def _refused(eng, storms, dtype):
+    """tcr_integrate_steps_*_host with a record block one double short: an error, and nothing left set in the context"""
+    import ctypes as C
+    from tropical_cyclone_risk_amd import _lib
+    n, rt = 4, (np.float32 if dtype == 'f32' else np.float64)
+    f64 = lambda k: np.ascontiguousarray(np.asarray(storms[k])[:n], dtype=np.float64)
+    ins = [f64(k) for k in ('lon', 'lat', 'v0', 'm0', 'h_bl')] + [np.ascontiguousarray(np.asarray(storms['month'])[:n] - 1, dtype=np.int32),
+                                                                   f64('phases').reshape(n, -1)]
+    outs = [np.empty((n, eng.n_steps), rt) for _ in range(5)] + [np.empty((n, eng.n_steps, 4), rt)] + [np.zeros(n, np.int32) for _ in range(6)]
+    si = _lib.Storms(n, *[a.ctypes.data for a in ins])
+    so = _lib.Tracks(*[a.ctypes.data for a in outs])
+    raw = np.zeros(n * 64 * (20 if dtype == 'f32' else 36) - 1)
+    fn = eng.L.tcr_integrate_steps_f32_host if dtype == 'f32' else eng.L.tcr_integrate_steps_host
+    rc = fn(eng.h, C.byref(si), C.byref(so), raw.ctypes.data_as(_lib.DP), raw.size)
+    msg = eng.L.tcr_last_error(eng.h).decode()
+    return rc != 0 and 'steps must hold' in msg and not raw.any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dtype', ['f32', 'f64'])
+def test_device_steps(golden_env, built_lib, dtype):
+    """Checks 1 to 7 of the module docstring on the records of k_integrate<float> / <double>: the first 256 GL candidates of E_YEAR
+    as eng.seed gives them, month slots as seeded, the golden environment, the host entry point with all rows.  The batch was
+    checked on the CPU first, with the C oracle on the same candidates (test_device_batch_meets_its_conditions_by_the_oracle).
+    Check 3 is asserted bit for bit against the probe of the run's type; check 4 in float32 against the C oracle on the
+    float-rounded data within C_BOUNDS of (1 + s + 2) twin + 2^-24 mag, in float64 against the float64 probe at the unfused stage
+    input within C_BOUNDS of (1 + s + 2) twin64 + 2^-53 mag (twin64: the oracle's response to one float64 ulp), and, where check 2
+    finds that a form — all fused, none fused, or DEVICE_FORM — reproduces every y_new bit for bit, K[s] bit for bit against the
+    probe at that form's stage inputs.
+    Measured on the MI355X (MEASURED), fp32 / fp64: 162 integrated storms, 126 without a rejection, 1 771 records;
+      check 2  max |y_old[j+1] - y_new_ref| / bound 0.970 / 0.961 (bound 1); y_new reproduced bit for bit by the fully fused form on
+               95.9 / 100 % of the pairs, by the unfused form on 83.2 / 83.0 %, by DEVICE_FORM — what the compiler emitted — on
+               100 / 100 %;
+      check 3  0 of 1 771 evaluations differ from the probe;
+      check 4  7 962 / 7 963 of 8 855 stage points kept, at least 1 583 per stage; max normalised error dlon 2.52 / 3.07, dlat
+               1.28 / 2.78, dv 0.86 / 0.63, dm 0.99 / 0.82 (bounds 30, 8, 7, 8); strongest form: all 8 855 K[1..5] equal the
+               probe at DEVICE_FORM's stage inputs and (fused) stage times bit for bit, in both types (asserted for every form
+               that reproduces every y_new; with the stage time rounded twice, 111 of the fp64 K[1..4] differ in their last bits);
+      check 5  1 609 pairs, 947 of storms without a rejection; next h at most 0.333 / 1.000 half widths from the middle of its
+               interval; max err - 1 - bound -2.1e-3 / -2.0e-3; first h within 2.2e-16 of select_initial_step (bound 1e-12);
+      check 6  24 301 / 24 312 rows; check 7: parked 124, 58, 30 storms in three passes; 88 storms overflow a record of 8."""
+    from tropical_cyclone_risk_amd import _lib
+    R = np.float32 if dtype == 'f32' else np.float64
+    eng = _engine(golden_env)
+    try:
+        s = eng.seed(E_YEAR, 0, N_CAND)
+        storms = {k: s[k] for k in ('lon', 'lat', 'v0', 'm0', 'h_bl', 'month', 'phases')}
+        P = eng.params
+        prm = dataclasses.replace(_prm(), total_time=float(P.total_time), rtol=float(P.rtol), atol=float(P.atol), max_step=float(P.max_step),
+                                  v_thresh=float(P.v_thresh), v_2d_thresh=float(P.v_2d_thresh))
+        assert prm.n_steps == eng.n_steps and int(P.max_rk_steps) == 64
+        plain = eng.integrate(storms, dtype=dtype, steps=True)
+        b = device_batch(eng, storms, dtype, plain)
+        on = integrated(b)
+        nrec = int(b['steps_n'].sum())
+        clean = int((b['n_reject'][on] == 0).sum())
+        assert len(on) >= 80 and clean >= 30 and nrec >= 1500 and (b['n_accept'] <= 64).all()
+        assert (b['status'] == EVENT).any() and (b['status'] == FINISHED).any()
+        assert (_lib.STATUS_GATED, _lib.STATUS_FINISHED, _lib.STATUS_EVENT, _lib.STATUS_STEP_OVERFLOW) == (GATED, FINISHED, EVENT, STEP_OVERFLOW)
+        Fs = eng.fourier_table(storms['phases'])
+
+        def probe(i, t, y):
+            y = np.asarray(y, np.float64)
+            d = eng.probe_rhs(int(storms['month'][i]) - 1, float(storms['h_bl'][i]), Fs[i], np.asarray(t, np.float64), y[:, 0], y[:, 1], y[:, 2], y[:, 3], dtype=dtype)[0]
+            assert np.array_equal(d, d.astype(R).astype(np.float64), equal_nan=True)
+            return d.astype(R)
+        # ---- 1
+        check_chain(b, prm, 64)
+        # ---- 2
+        ratio, share = check_y_new(b)
+        print('%s: %d integrated storms (%d without a rejection), %d records' % (dtype, len(on), clean, nrec))
+        print('check 2: max |y_old[j+1] - y_new_ref| / bound %.3f per component %s; reproduced bit for bit by the fully fused form %.4f, by the unfused form %.4f, '
+              'by a fused sum with a separate last operation %.4f, by a separate sum with a fused last operation %.4f, by DEVICE_FORM %.4f'
+              % ((ratio.max(), np.round(ratio.max(axis=0), 3), share[True], share[False]) + share['mixed'] + (share['device'],)))
+        assert ratio.max() <= 1.0
+        # ---- 3
+        bad, total = check_endpoints(b, probe)
+        print('check 3: %d of %d evaluations at exactly known inputs differ from the probe' % (bad, total))
+        assert bad == 0 and total == nrec
+        # ---- 4
+        orc = OracleRhs(golden_env, storms, R)
+        sr = StageReference(b, orc)
+        if dtype == 'f32':
+            e, st, kept, total = sr.errors(lambda i: b['rec'][i].K[:, 1:6])
+        else:
+            # the float64 probe at the unfused stage input takes the oracle's place as the value; the oracle gives the yardstick
+            for i in on:
+                t, y = stage_points(b, i)
+                sr.per[i]['ref'] = np.concatenate([probe(i, t.reshape(-1), y.reshape(-1, 4)), sr.per[i]['ref'][:, 4:]], axis=1)
+            e, st, kept, total = sr.errors(lambda i: b['rec'][i].K[:, 1:6])
+        per_stage = [int((st == k).sum()) for k in range(1, 6)]
+        print('check 4: %d of %d stage points kept (%s per stage); max normalised error dlon %.2f dlat %.2f dv %.2f dm %.2f'
+              % ((kept, total, per_stage) + tuple(e.max(axis=0))))
+        assert kept >= 0.5 * total and min(per_stage) >= 500
+        assert (e <= STAGE_BOUNDS).all(), e.max(axis=0)
+        forms = [('fused', True, None, True, share[True]), ('unfused', False, None, False, share[False]), ('device', ) + DEVICE_FORM[dtype] + (share['device'],)]
+        for name, fused, fused_last, fused_time, sh in forms:
+            if sh == 1.0 or name == 'device':
+                diff = np.zeros(5, int)
+                n_pts = 0
+                for i in on:
+                    t, y = stage_points(b, i, fused=fused, fused_last=fused_last, fused_time=fused_time)
+                    got = probe(i, t.reshape(-1), y.reshape(-1, 4)).reshape(y.shape)
+                    diff += (_bits(got) != _bits(b['rec'][i].K[:, 1:6])).any(axis=2).sum(axis=0); n_pts += t.size
+                print('check 4, strongest form: the %s form reproduces %.4f of the y_new; per stage %s of %d K[1..5] differ from the probe at its stage inputs'
+                      % (name, sh, diff, n_pts))
+                if sh == 1.0:
+                    assert diff.sum() == 0, (name, diff)
+        # ---- 5
+        ok, dist, over, cl = check_controller(b, prm)
+        print('check 5: %d pairs (%d of storms without a rejection); max distance from the predicted h in units of the tolerance %.3f; max err - 1 - bound %.3g'
+              % (len(ok), int(cl.sum()), dist.max(), over.max()))
+        assert (over < 0).all() and check_last_err(b, prm).all()
+        assert ok.all(), np.flatnonzero(~ok)[:8]
+        dev = check_first_step(b, prm, probe)
+        print('check 5: first step of %d storms without a rejection: max |h[0] / select_initial_step - 1| %.3g' % (len(dev), dev.max()))
+        assert len(dev) >= 30 and dev.max() <= 1e-12
+        # ---- 6
+        rows = check_dense(b, prm, planes=('lon', 'lat', 'v', 'm', 'vmax', 'envw'))
+        print('check 6: %d rows bit-identical' % rows)
+        assert rows > 10000
+        # ---- the instrument itself: the run without it gives the same planes and counters; a block of the wrong size is refused
+        base = eng.integrate(storms, dtype=dtype)
+        for k in ('lon', 'lat', 'v', 'm', 'vmax', 'envw') + COUNTERS[:5] + ('flags',):
+            assert np.array_equal(base[k], plain[k], equal_nan=True), k
+        assert _refused(eng, storms, dtype)
+        # ---- 7
+        eng.tune(waves=4, park=32, park_final=1)
+        try:
+            parked = eng.integrate(storms, dtype=dtype, steps=True)
+            stats = eng.pass_stats()
+        finally:
+            eng.tune(waves=-1, park=-1, park_final=-1)
+        assert sum(1 for p in stats if p['parked'] > 0) >= 2, stats
+        for k in COUNTERS:
+            assert np.array_equal(plain[k], parked[k]), k
+        for i in on:
+            assert _records_equal(plain, parked, i, int(plain['steps_n'][i])), i
+        print('check 7: %d passes, parked %s: records and counters identical' % (len(stats), [p['parked'] for p in stats]))
+    finally:
+        eng.close()
+    short_eng = _engine(golden_env, max_rk=8)
+    try:
+        short = short_eng.integrate(storms, dtype=dtype, steps=True)
+    finally:
+        short_eng.close()
+    assert short['steps_y'].shape[1] == 8
+    long_ = plain['n_accept'] >= 8
+    over8 = plain['n_accept'] > 8
+    assert over8.sum() >= 20
+    for i in on:
+        m = min(int(plain['steps_n'][i]), 8)
+        assert short['steps_n'][i] == m and all(_same(plain[k][i, :m], short[k][i, :m]) for k in STEP_KEYS), i
+    assert (short['steps_n'][on][long_[on]] == 8).all()
+    assert (short['status'][over8] == STEP_OVERFLOW).all() and (short['n_accept'][over8] == 8).all()
+    assert np.array_equal(short['status'][~long_], plain['status'][~long_])
+    print('check 7: %d storms overflow a record of 8; their 8 records are the plain run\'s first 8' % int(over8.sum()))

@@ -44,7 +44,7 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_windfield_pairs', 'tcr_loss_dev', 'tcr_loss_host', 'tcr_rainfall_dev', 'tcr_rainfall_host', 'tcr_rainfall_pairs',
            'tcr_compound_dev', 'tcr_compound_host', 'tcr_compound_pairs', 'tcr_duration_dev', 'tcr_duration_host', 'tcr_duration_pairs',
            'tcr_select_dev', 'tcr_select_host', 'tcr_tail_dev', 'tcr_tail_host',
-           'tcr_probe_rhs_f32_host')
+           'tcr_probe_rhs_f32_host', 'tcr_integrate_steps_host', 'tcr_integrate_steps_f32_host')
 TCR_COMM_ID_BYTES = 128
 
 
@@ -222,6 +222,8 @@ def lib():
     L.tcr_masks_upload.argtypes = [C.c_void_p, C.POINTER(Grid), U8P, C.POINTER(U8P)]
     L.tcr_integrate_host.argtypes = [C.c_void_p, C.POINTER(Storms), C.POINTER(Tracks)]
     L.tcr_integrate_probe_host.argtypes = [C.c_void_p, C.POINTER(Storms), C.POINTER(Tracks), C.c_void_p, C.c_int32]
+    L.tcr_integrate_steps_host.argtypes = [C.c_void_p, C.POINTER(Storms), C.POINTER(Tracks), DP, C.c_int64]
+    L.tcr_integrate_steps_f32_host.argtypes = [C.c_void_p, C.POINTER(Storms), C.POINTER(Tracks), DP, C.c_int64]
     L.tcr_integrate_f32_dev.argtypes = [C.c_void_p, C.POINTER(Storms), C.POINTER(Tracks), C.c_void_p]    # tcr_tracks_f32 has tcr_tracks' layout
     L.tcr_integrate_f32_host.argtypes = [C.c_void_p, C.POINTER(Storms), C.POINTER(Tracks)]
     L.tcr_integrate_dev.argtypes = [C.c_void_p, C.POINTER(Storms), C.POINTER(Tracks), C.c_void_p]

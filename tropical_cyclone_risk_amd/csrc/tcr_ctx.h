@@ -147,6 +147,7 @@ struct IntegrateWs {
     DevArray<int64_t> d_tc_count;
     uint8_t *d_probe = nullptr;                 // decision probe of the next tcr_integrate_dev (tcr_integrate_probe_host; that call's DevBuf owns it)
     int probe_cap = 0;
+    double *d_steps = nullptr;                  // where the next batch's step records are copied before k_dense rewrites them (tcr_integrate_steps_*_host; that call's DevBuf owns it)
 };
 
 struct RoundGraph { std::vector<uint8_t> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; bool failed = false; };

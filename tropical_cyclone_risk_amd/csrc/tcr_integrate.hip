@@ -336,6 +336,8 @@ int integrate_impl(tcr_ctx *ctx, const tcr_storms *in, const TracksT<R> out, voi
         if (ev && !seg_events) { HIPCHK(ctx, hipEventRecord(ev[4], st)); HIPCHK(ctx, hipEventRecord(ev[5], st)); }
     }
     STAGE(TCR_STAGE_INTEGRATE);
+    // test instrument (tcr_integrate_steps_*_host): the records as k_integrate left them — K[7][4], before k_dense puts Q in its place
+    if (W.d_steps) HIPCHK(ctx, hipMemcpyAsync(W.d_steps, W.d_srec.p, sizeof(double) * (size_t)n * max_rk * REC, hipMemcpyDeviceToDevice, st));
     if (ev) HIPCHK(ctx, hipEventRecord(ev[2], st));
     {
         EArgsT<R> a{};
@@ -439,6 +441,31 @@ int integrate_host_impl(tcr_ctx *ctx, const tcr_storms *in, const T *out)
         d2h(ctx, out->n_valid, dout.n_valid, n) || d2h(ctx, out->status, dout.status, n) || d2h(ctx, out->flags, dout.flags, n) ||
         d2h(ctx, out->nfev, dout.nfev, n) || d2h(ctx, out->n_accept, dout.n_accept, n) || d2h(ctx, out->n_reject, dout.n_reject, n))
         return -1;
+    return 0;
+}
+
+// tcr_integrate_*_host plus the batch's accepted-step records (integrate_impl copies them while IntegrateWs::d_steps is set)
+template <typename R, typename T>
+int integrate_steps_impl(tcr_ctx *ctx, const char *who, const tcr_storms *in, const T *out, double *steps, int64_t steps_doubles)
+{
+    if (!ctx) return -1;
+    if (!in || !out || !steps) return fail(ctx, "%s: NULL argument", who);
+    if (ready(ctx, false)) return -1;
+    if (ctx->ws.d_probe || ctx->ws.d_steps) return fail(ctx, "%s: another instrument of the integrator is active", who);
+    if (!enter(ctx)) return -1;
+    if (in->n <= 0) return 0;
+    const int max_rk = ctx->prm.max_rk_steps > 0 ? ctx->prm.max_rk_steps : 64;
+    const size_t need = (size_t)in->n * (size_t)max_rk * (size_t)step_rec_doubles<R>();
+    if (steps_doubles < 0 || (size_t)steps_doubles != need)
+        return fail(ctx, "%s: steps must hold n x max_rk_steps x step-record doubles (36 fp64, 20 fp32)", who);
+    DevBuf B;
+    double *d = B.get<double>(need);
+    if (!d) return fail(ctx, "%s: device allocation failed", who);
+    ctx->ws.d_steps = d;
+    const int rc = integrate_host_impl<R>(ctx, in, out);
+    ctx->ws.d_steps = nullptr;
+    if (rc) return rc;
+    HIPCHK(ctx, copy_sync(ctx->stream, steps, d, sizeof(double) * need, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -567,6 +594,7 @@ int tcr_integrate_dev(tcr_ctx *ctx, const tcr_storms *in, const tcr_tracks *out,
 {
     if (ready(ctx, false)) return -1;
     if (!in || !out) return fail(ctx, "tcr_integrate_dev: NULL argument");
+    if (ctx->ws.d_steps) return fail(ctx, "the step records are an instrument of the host entry points");
     return integrate_impl<double>(ctx, in, tracks_of<double>(out), stream_);
 }
 
@@ -575,6 +603,7 @@ int tcr_integrate_f32_dev(tcr_ctx *ctx, const tcr_storms *in, const tcr_tracks_f
     if (ready(ctx, false)) return -1;
     if (!in || !out) return fail(ctx, "tcr_integrate_f32_dev: NULL argument");
     if (ctx->ws.d_probe) return fail(ctx, "the decision probe is an fp64 instrument");
+    if (ctx->ws.d_steps) return fail(ctx, "the step records are an instrument of the host entry points");
     hipStream_t st = enter(ctx, stream_);
     if (!st || ensure_f32(ctx, st)) return -1;
     return integrate_impl<float>(ctx, in, tracks_of<float>(out), stream_);
@@ -608,6 +637,16 @@ int tcr_integrate_probe_host(tcr_ctx *ctx, const tcr_storms *in, const tcr_track
     if (rc) return rc;
     HIPCHK(ctx, copy_sync(ctx->stream, dec, d, bytes, hipMemcpyDeviceToHost));
     return 0;
+}
+
+int tcr_integrate_steps_host(tcr_ctx *ctx, const tcr_storms *in, const tcr_tracks *out, double *steps, int64_t steps_doubles)
+{
+    return integrate_steps_impl<double>(ctx, "tcr_integrate_steps_host", in, out, steps, steps_doubles);
+}
+
+int tcr_integrate_steps_f32_host(tcr_ctx *ctx, const tcr_storms *in, const tcr_tracks_f32 *out, double *steps, int64_t steps_doubles)
+{
+    return integrate_steps_impl<float>(ctx, "tcr_integrate_steps_f32_host", in, out, steps, steps_doubles);
 }
 
 int tcr_fourier_table_host(tcr_ctx *ctx, int64_t n, const double *phases, double *Fs)

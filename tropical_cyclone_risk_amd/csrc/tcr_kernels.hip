@@ -607,7 +607,8 @@ template <typename R> constexpr int int_wps() { return sizeof(R) == 8 ? TCR_INT_
 template <typename R, bool AFFINE, bool PROBE, int SM>
 __global__ __launch_bounds__(kWave, (int_wps<R>())) void k_integrate(KArgsT<R> a)
 {
-    // TCR_FUSE_RK (tcr_device.h): stage inputs, y_new, the error norm and the initial-step norms below contract to fmas; nothing
+    // TCR_FUSE_RK (tcr_device.h): stage inputs, stage times (t + C_s h), y_new, the error norm and the initial-step norms below may contract to fmas
+    // (which of them do is the compiler's choice per site: tests/test_rk_steps.py DEVICE_FORM has what it chose); nothing
     // inlined from another function does — in particular not the helpers of accept test 1 (dense_v_*), which k_screen shares
     TCR_FP_FUSE_RK
     // Kl[(stage*4 + component)*64 + lane]

@@ -322,6 +322,7 @@ int tcr_round_dev(tcr_ctx *ctx, const tcr_round *r, uint64_t seed, int32_t year,
         !r->storms.basin_idx || !r->tracks.flags || !r->tracks.n_valid)
         return fail(ctx, "tcr_round_dev: NULL buffer");
     if (r->cell_deg != 0 && !(r->cell_deg >= 0.25 && r->cell_deg <= 90.0)) return fail(ctx, "tcr_round_dev: cell_deg must be 0 or in [0.25, 90]");
+    if (ctx->ws.d_steps) return fail(ctx, "the step records are an instrument of the host entry points");
     hipStream_t st = enter(ctx, stream_);
     if (!st) return -1;
     if (!use_graph || ctx->ws.d_probe) return enqueue_round(ctx, r, seed, year, cand0, nullptr, st);

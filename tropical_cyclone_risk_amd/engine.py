@@ -229,14 +229,17 @@ class TCEngine:
             self._ck(self.L.tcr_init_m_host(self.h, C.byref(si), float(dvdt), _dp(out)))
         return out
 
-    def integrate(self, storms, probe_cap=0, dtype='f64'):
+    def integrate(self, storms, probe_cap=0, dtype='f64', steps=False):
         """Integrate + post-process a batch given as host arrays (dict with lon, lat, v0,
         m0, h_bl, month (1..12), phases [n,4,N]); returns a dict of NumPy arrays.  probe_cap > 0 adds
         'dec' [n, probe_cap] uint8, the per-evaluation `land == 1` decisions (tcr_integrate_probe_host).
         dtype='f32': the fp32 variant (tcr_integrate_f32_host), rows come back as float32.
         gen_track(m=None) (coupled_fast.py:258-261): a batch without 'm0' gets it from `init_m` (dv/dt = 0 at t = 0) first.
         (A NaN *entry* of a given m0 is not "None": the reference integrates it as it is, and so does this — call `init_m`
-        explicitly to fill NaN entries.)"""
+        explicitly to fill NaN entries.)
+        steps=True (tests; tcr_integrate_steps_host / _f32_host) adds the accepted-step records as k_integrate left them:
+        'steps_t_old', 'steps_h', 'steps_t_new' [n, max_rk] float64, 'steps_y' [n, max_rk, 4] and 'steps_K' [n, max_rk, 7, 4] in the
+        run's type, 'steps_n' = min(n_accept, max_rk) (0 for gated storms).  Records at and beyond steps_n are stale memory."""
         n = len(storms['lon'])
         ns = self.n_steps
         if n and storms.get('m0') is None:
@@ -244,15 +247,18 @@ class TCEngine:
         lon0, lat0, v0, m0, h_bl = (_f64(storms[k]) for k in ('lon', 'lat', 'v0', 'm0', 'h_bl'))
         slot = np.ascontiguousarray(np.asarray(storms['month']) - 1, dtype=np.int32)
         ph = _f64(storms['phases']).reshape(n, 4 * self.n_series)
-        assert dtype in ('f64', 'f32') and not (probe_cap and dtype == 'f32')
+        assert dtype in ('f64', 'f32') and not (probe_cap and dtype == 'f32') and not (probe_cap and steps)
         rt = np.float64 if dtype == 'f64' else np.float32
         out = {k: np.empty((n, ns), rt) for k in TRACK_F64}
         out['envw'] = np.empty((n, ns, 4), rt)
         out.update({k: np.zeros(n, np.int32) for k in TRACK_I32})
+        max_rk = int(self.params.max_rk_steps) if int(self.params.max_rk_steps) > 0 else 64
+        rec = 4 + (32 if dtype == 'f64' else 16)            # step_rec_doubles<R>()
+        raw = np.zeros((n, max_rk, rec)) if steps else None
         if n == 0:
             if probe_cap:
                 out['dec'] = np.full((0, int(probe_cap)), 0xff, np.uint8)
-            return self._finish(out)
+            return self._finish(self._steps(out, raw, rt))
         si = _lib.Storms(n, *[a.ctypes.data for a in (lon0, lat0, v0, m0, h_bl, slot, ph)])
         so = _lib.Tracks(*[out[k].ctypes.data for k in ('lon', 'lat', 'v', 'm', 'vmax', 'envw',
                                                          'n_valid', 'status', 'flags', 'nfev',
@@ -260,11 +266,27 @@ class TCEngine:
         if probe_cap:
             out['dec'] = np.full((n, int(probe_cap)), 0xff, np.uint8)
             self._ck(self.L.tcr_integrate_probe_host(self.h, C.byref(si), C.byref(so), out['dec'].ctypes.data, int(probe_cap)))
+        elif steps:
+            fn = self.L.tcr_integrate_steps_f32_host if dtype == 'f32' else self.L.tcr_integrate_steps_host
+            self._ck(fn(self.h, C.byref(si), C.byref(so), _dp(raw), raw.size))
         elif dtype == 'f32':
             self._ck(self.L.tcr_integrate_f32_host(self.h, C.byref(si), C.byref(so)))
         else:
             self._ck(self.L.tcr_integrate_host(self.h, C.byref(si), C.byref(so)))
-        return self._finish(out)
+        return self._finish(self._steps(out, raw, rt))
+
+    @staticmethod
+    def _steps(out, raw, rt):
+        """The raw record block [n, max_rk, REC] doubles (tcr_device.h: kStepHdr) as named arrays."""
+        if raw is None:
+            return out
+        n, max_rk = raw.shape[:2]
+        out['steps_t_old'], out['steps_h'], out['steps_t_new'] = (np.ascontiguousarray(raw[:, :, k]) for k in range(3))
+        body = np.ascontiguousarray(raw[:, :, 4:]).view(rt).reshape(n, max_rk, 8, 4)
+        out['steps_y'] = np.ascontiguousarray(body[:, :, 0])
+        out['steps_K'] = np.ascontiguousarray(body[:, :, 1:])
+        out['steps_n'] = np.where(out['status'] == _lib.STATUS_GATED, 0, np.minimum(out['n_accept'], max_rk)).astype(np.int32)
+        return out
 
     @staticmethod
     def _finish(out):
