@@ -9,16 +9,32 @@
 // The [n_site][n_trk] planes that would carry W and P to a joint count elsewhere are optional here: the histogram is built where
 // the two values are still in registers.
 //
-// A user of the site scan (tcr_sitescan.h: tiling, culling, counts; its kJoint variant).  What is the compound's own:
+// A user of the site scan (tcr_sitescan.h: tiling, culling, the mode protocol).  What is the compound's own:
 //   CpRec             one sample or sub-sample (160 bytes): the position terms once, then the wind terms of WfRec and the rain
 //                     terms of RfRec;
 //   k_compound_prep   one wave per storm: finds the track over the eight planes (ballot), stages the footprint's per-sample terms
 //                     (wf_stage), then writes one record per sample and sub-sample: wf_sub_record and rf_sub_record side by side;
 //   CompoundScan      the policy of k_site_scan: WindScan's value under the wind radius, RainScan's under the rain radius, on the
-//                     one angle the scan forms per included pair.
+//                     one angle ScanJoint forms per included pair;
+//   ScanJoint<SUM>    the mode: two hazards of one record at once.  The scan includes a pair under the larger radius (a_R and r_ang,
+//                     the culling, are that radius's); the pair's angle is formed once; first(site, record, angle) goes into a max
+//                     under the policy's a_first and second(site, record, angle) into a max, or with SUM into a sum in record
+//                     order, under its a_second.  site_max takes the first, the policy's site_second the second.  thr holds the
+//                     n_first thresholds of the first, then the n_second of the second, and the histogram is two-dimensional:
+//                     n_cell = (n_first + 1) (n_second + 1) and counts[site][group][a (n_second + 1) + b] = #storms of the group
+//                     passing at least a thresholds of the first and at least b of the second (a NaN passes none, so index 0 is
+//                     "no condition" and [0][0] the size of the group).
+//                     A wave's histogram is its LDS, and 64 cells of int32 per lane (16 KB) leave room for 9 waves on a CU: the
+//                     joint scan ran at 2 waves / SIMD and 1.6 x slower than with 9 cells (profiles/compound_bench.txt).  So its
+//                     cells are kJointHist (16 bits), and the plan keeps a chunk at kJointMaxChunk storms or fewer, which no cell
+//                     and no suffix sum can exceed.
 // No formula is restated here: records, interpolation and per-pair values are the footprint's and the rainfall's own functions.
 //
-// Bit-identity: tcr_sitescan.h's argument for kJoint.  A record's position terms are the same bits in wf_sub_record and
+// Bit-identity.  Each of ScanJoint's two accumulators sees exactly the records with a <= its own a threshold, in record order, and
+// nothing else: the cull uses the larger radius, so it is conservative for both; the test of one hazard never gates the other; the
+// values come from the functions the single-hazard policies call, on the same record terms and the same angle expression.  So each
+// plane is bit for bit what the single-hazard scan of that policy writes (tcr_sitescan.h: one lane, one accumulator), and the 2-D
+// counts are integer sums of per-storm ranks of those values.  A record's position terms are the same bits in wf_sub_record and
 // rf_sub_record (the same expressions of the same lon, lat and tau; the build has no contraction), so keeping the footprint's
 // copy changes nothing for the rain.  With all eight planes finite on a storm's track W and P are bit for bit the two entry
 // points' outputs, whatever the launch shape, the site order and the storm order; the counts are integers.
@@ -77,14 +93,67 @@ __global__ __launch_bounds__(64) void k_compound_prep(CpPrepArgs a)
     scan_finish_row(a.out, s, nr);
 }
 
-// the policy of k_site_scan<CompoundScan<UNIT_C, SUM>>: the kJoint variant with the footprint's wind first and the rainfall's value
-// (SUM: the storm total, otherwise the peak rate) second
+using kJointHist = uint16_t;                // a cell of the joint scan's LDS histogram
+constexpr int64_t kJointMaxChunk = 65535;   // storms of a chunk it can count
+
+// the mode of CompoundScan (header comment); cells [n_first + 1][n_second + 1][64] of kJointHist: the storms of this lane passing
+// exactly (kw, kr) thresholds of each list
+template <bool SUM>
+struct ScanJoint {
+    struct Storm { double m = NAN, m2 = NAN; };
+    // thr: the first list, then the second (n_first + n_second of them)
+    static ScanShape shape(int32_t n_first, int32_t n_second, const double *thr)
+    {
+        const int32_t n_cell = (n_first + 1) * (n_second + 1);
+        return ScanShape{n_cell, sizeof(kJointHist) * 64 * (n_cell + 1), n_first + n_second, thr};      // (begin zeroes n_cell + 1 cells)
+    }
+    template <class P> __device__ __forceinline__ void begin(const P &, const ScanLane &c)
+    {
+        kJointHist *hist = reinterpret_cast<kJointHist *>(c.lds);
+        for (int k = 0; k <= c.a.n_cell; ++k) hist[k * 64 + c.lane] = 0;
+    }
+    template <class P, class Rec> __device__ __forceinline__ void add(const P &pol, Storm &st, const ScanSite &me, const Rec &p, double q)
+    {
+        const double ang = scan_pair_angle(q);          // q <= a_R, the larger radius; then each hazard under its own
+        if (q <= pol.a_first) st.m = fmax(st.m, pol.first(me, p, ang));
+        if (q <= pol.a_second) {
+            const double v = pol.second(me, p, ang);
+            if constexpr (SUM) st.m2 = isnan(st.m2) ? v : st.m2 + v;            // in record order
+            else st.m2 = fmax(st.m2, v);
+        }
+    }
+    template <class P> __device__ __forceinline__ void end_storm(const P &pol, const ScanLane &c, const Storm &st, int64_t s, bool)
+    {
+        kJointHist *hist = reinterpret_cast<kJointHist *>(c.lds);
+        if (c.a.site_max && c.valid) c.a.site_max[c.site * c.a.n_trk + s] = st.m;
+        if (pol.site_second && c.valid) pol.site_second[c.site * c.a.n_trk + s] = st.m2;
+        // every storm is counted: a NaN has rank 0
+        const int kw = scan_rank(c.a.thr, pol.n_first, st.m), kr = scan_rank(c.a.thr + pol.n_first, pol.n_second, st.m2);
+        hist[(kw * (pol.n_second + 1) + kr) * 64 + c.lane] += 1;
+    }
+    template <class P> __device__ __forceinline__ void end_chunk(const P &pol, const ScanLane &c)
+    {
+        kJointHist *hist = reinterpret_cast<kJointHist *>(c.lds);
+        const int lane = c.lane;
+        // exactly (kw, kr) -> at least (kw, kr): suffix sums along the second axis, then along the first, in the lane's own column
+        const int nw = pol.n_first, nr = pol.n_second;
+        for (int kw = nw; kw >= 0; --kw)
+            for (int kr = nr - 1; kr >= 0; --kr) hist[(kw * (nr + 1) + kr) * 64 + lane] += hist[(kw * (nr + 1) + kr + 1) * 64 + lane];
+        for (int kw = nw - 1; kw >= 0; --kw)
+            for (int kr = nr; kr >= 0; --kr) hist[(kw * (nr + 1) + kr) * 64 + lane] += hist[((kw + 1) * (nr + 1) + kr) * 64 + lane];
+        if (!c.valid) return;
+        int32_t *out = c.a.part + (c.chunk * c.a.n_site + c.site) * c.a.n_cell;
+        for (int b = 0; b < c.a.n_cell; ++b) out[b] = hist[b * 64 + lane];
+    }
+};
+
+// the policy of k_site_scan<CompoundScan<UNIT_C, SUM>>: the footprint's wind first and the rainfall's value (SUM: the storm total,
+// otherwise the peak rate) second
 template <bool UNIT_C, bool SUM>
 struct CompoundScan {
     using Rec = CpRec;
+    using Mode = ScanJoint<SUM>;
     static constexpr int kUnroll = 2;
-    static constexpr bool kJoint = true;
-    static constexpr bool kSecondSum = SUM;
     WindScan<UNIT_C> wind;
     double a_first, a_second;               // a thresholds of wind.r_out_km and rain.r_out_km
     int32_t n_first, n_second;              // n_wbin, n_rbin
@@ -119,12 +188,12 @@ int compound_check(tcr_ctx *ctx, const tcr_wind_tracks *t, const double *vmax, c
 
 template <bool UNIT_C, bool SUM>
 hipError_t compound_launch(const CpPrepArgs &p, const tcr_wind_params *wp, const tcr_rain_params *rp, int32_t n_wbin, int32_t n_rbin,
-                           double *site_rain, const ScanArgs<CpRec> &m, dim3 grid, size_t lds, hipStream_t st)
+                           double *site_rain, const ScanLaunch &L)
 {
-    const double c = wp->ck_cd, re_km = kWfEarthR / 1000.0;
-    return scan_launch(k_compound_prep, p, p.wf.n_trk, m, grid, lds, st,
-                       CompoundScan<UNIT_C, SUM>{{c, 2.0 - c, 1.0 / (2.0 - c)}, scan_a_of(wp->r_out_km, re_km),
-                                                 scan_a_of(rp->r_out_km, re_km), n_wbin, n_rbin, site_rain});
+    const double re_km = kWfEarthR / 1000.0;
+    return scan_launch(k_compound_prep, p, p.out, L,
+                       CompoundScan<UNIT_C, SUM>{wind_scan<UNIT_C>(wp), scan_a_of(wp->r_out_km, re_km), scan_a_of(rp->r_out_km, re_km),
+                                                 n_wbin, n_rbin, site_rain});
 }
 
 }  // namespace
@@ -139,27 +208,21 @@ int tcr_compound_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const double *vmax,
     if (!st || compound_check(ctx, t, vmax, wp, rp, n_site, site_lon, site_lat, n_wbin, wthr, n_rbin, rthr, counts)) return -1;
     const int64_t n_rec = (t->n_t - 1) * wp->substeps + 1;
     const size_t n_stage = (size_t)std::max<int64_t>(1, t->n_trk * t->n_t);
-    double thr[kHzMaxBin] = {};                         // the wind list, then the rain list (n_wbin + n_rbin <= 32)
+    double thr[kHzMaxBin];                              // the wind list, then the rain list (n_wbin + n_rbin <= 32)
     for (int b = 0; b < n_wbin; ++b) thr[b] = wthr[b];
     for (int b = 0; b < n_rbin; ++b) thr[n_wbin + b] = rthr[b];
     const tcr_hazard_tracks ht = compound_rain_tracks(t, vmax);
-    return scan_run<CpRec>(ctx, ctx->an.cp, "tcr_compound", t, n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat,
-                           std::max(wp->r_out_km, rp->r_out_km), kWfEarthR / 1000.0, (n_wbin + 1) * (n_rbin + 1), thr, counts, site_wind,
-                           st, [&](const ScanArgs<CpRec> &m, void *stage, dim3 grid, size_t) {
-        const size_t lds = sizeof(kJointHist) * 64 * (m.n_bin + 1);      // (the scan zeroes n_bin + 1 rows)
-        CpPrepArgs p{};
-        p.wf = WfPrepArgs{t->lon, t->lat, t->v, t->u250, t->v250, t->u850, t->v850, t->rmax_km, t->n_trk, t->n_t, t->row_stride,
-                          wp->dt_s, wp->rmax_const_km, wp->substeps, static_cast<WfStage *>(stage), ScanRows<WfRec>{}};
-        p.rf = RfPrepArgs{ht.lon, ht.lat, ht.vmax, ht.n_trk, ht.n_t, ht.row_stride, rp->dt_s / (3600.0 * rp->substeps), rp->v_lo_kt,
-                          rp->v_hi_kt, {rp->a[0], rp->a[1], rp->a[2], rp->a[3]}, {rp->b[0], rp->b[1], rp->b[2], rp->b[3]},
-                          rp->substeps, ScanRows<RfRec>{}};
-        p.out = m.rows;
+    // (both stats' modes have the one shape)
+    return scan_run<CpRec>(ctx, ctx->an.cp, "tcr_compound", t, scan_plan(t, n_site, kJointMaxChunk), ScanJoint<true>::shape(n_wbin, n_rbin, thr),
+                           n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat, std::max(wp->r_out_km, rp->r_out_km),
+                           kWfEarthR / 1000.0, counts, site_wind, st, [&](const ScanRows<CpRec> &rows, const ScanLaunch &L, void *stage) {
+        const CpPrepArgs p{wind_prep_args(t, wp, stage, ScanRows<WfRec>{}), rain_prep_args(&ht, rp, ScanRows<RfRec>{}), rows};
         const bool unit = wp->ck_cd == 1.0, sum = rp->stat == TCR_RAIN_TOTAL;
-        if (unit && sum) return compound_launch<true, true>(p, wp, rp, n_wbin, n_rbin, site_rain, m, grid, lds, st);
-        if (unit) return compound_launch<true, false>(p, wp, rp, n_wbin, n_rbin, site_rain, m, grid, lds, st);
-        if (sum) return compound_launch<false, true>(p, wp, rp, n_wbin, n_rbin, site_rain, m, grid, lds, st);
-        return compound_launch<false, false>(p, wp, rp, n_wbin, n_rbin, site_rain, m, grid, lds, st);
-    }, kJointMaxChunk);
+        if (unit && sum) return compound_launch<true, true>(p, wp, rp, n_wbin, n_rbin, site_rain, L);
+        if (unit) return compound_launch<true, false>(p, wp, rp, n_wbin, n_rbin, site_rain, L);
+        if (sum) return compound_launch<false, true>(p, wp, rp, n_wbin, n_rbin, site_rain, L);
+        return compound_launch<false, false>(p, wp, rp, n_wbin, n_rbin, site_rain, L);
+    });
 }
 
 int tcr_compound_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const double *vmax, const tcr_wind_params *wp, const tcr_rain_params *rp,

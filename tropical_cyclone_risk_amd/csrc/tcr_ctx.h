@@ -91,13 +91,16 @@ struct CopyPool {
     }
 };
 
-// Workspace of one site-scan analysis (tcr_sitescan.h), blocks in bytes.  d: records, caps, record counts, partial counts, chunk
-// table + pair counter, the prep kernel's own, two of the analysis's own; h: the pinned staging of the chunk table.
+// The blocks of ScanWs::d: records, caps (storms, then segments), record counts, partial counts, chunk table + pair counter, the
+// prep kernel's own, two of the analysis's own.
+enum { kWsRec, kWsCaps, kWsCnt, kWsPart, kWsTab, kWsPrep, kWsOwn0, kWsOwn1, kWsBlocks };
+
+// Workspace of one site-scan analysis (tcr_sitescan.h), blocks in bytes.  h: the pinned staging of the chunk table.
 struct ScanWs {
-    DevArray<char> d[8];
+    DevArray<char> d[kWsBlocks];
     PinnedArray<int64_t> h;
     hipEvent_t ev = nullptr, done = nullptr;        // chunk table uploaded / last call done
-    unsigned long long *pairs = nullptr;            // pairs the last call evaluated (inside d[4])
+    unsigned long long *pairs = nullptr;            // pairs the last call evaluated (inside d[kWsTab])
     ~ScanWs() { destroy_events(&ev, 1); destroy_events(&done, 1); }
 };
 

@@ -8,19 +8,33 @@
 //   counts[site][group][l][b]   = #storms of the group with site_hours >= thresholds[b]
 //   half_steps[site][group][l]  = sum of H over the storms of the group                                                 (int64)
 //
-// A user of the site scan (tcr_sitescan.h: tiling, culling, counts; its kLevels variant) on the wind footprint's records: the prep
-// kernel is k_wind_prep itself, the wind of a pair is WindScan's.  What is the duration's own:
+// A user of the site scan (tcr_sitescan.h: tiling, culling, the mode protocol) on the wind footprint's records: the prep kernel is
+// k_wind_prep itself, the wind of a pair is WindScan's.  What is the duration's own:
 //   DuRec             WfRec read with its half-weight: the one record slot WfRec::uniform leaves alone;
 //   DurationScan      the policy of k_site_scan: WindScan's value, the record's half-weight, the levels and where the planes go;
+//   ScanLevels<NL>    the mode (1 <= NL <= kScanMaxLevel): time instead of a peak.  value(site, record, a) is formed once per
+//                     included pair and compared with the policy's NL ascending level[] (unused ones +inf), and the record's
+//                     integer weight(record) is added to the int32 accumulator of every level the value reaches (>=) and to one
+//                     more that counts the included records.  The NL + 1 accumulators are registers: fixed arrays, fully unrolled,
+//                     never indexed by a run-time value.  Per storm each of the policy's n_level levels has the value
+//                     (double)sum * unit (NaN when no record was included), which the lane that accumulated it writes to the
+//                     policy's site_level[l] (when not NULL) and ranks against the n_hbin thresholds in thr into the level's own
+//                     (n_hbin + 1) cells of the histogram.  The partial counts are [level][threshold]: n_cell = n_level n_hbin,
+//                     which k_hazard_reduce sums unchanged.  Every lane also keeps an int64 total of its sums per level over the
+//                     chunk's storms and writes it to the policy's level_part [n_chunk][n_site][n_level].  There is no max: the
+//                     call's site_max is NULL and nothing reads it;
 //   k_duration_reduce sums the int64 per-chunk totals of each group.
 // No formula is restated here.
 //
-// Bit-identity: tcr_sitescan.h's argument for kLevels.  Everything accumulated is an integer, so every output is the same bits
-// whatever the launch shape, the site order, the storm order and the chunking.  That is what the half-weights are for: a sum of
-// fp64 hours would depend on its order, and on the chunking once it crosses storms.
+// Bit-identity, by the scan's first argument alone (tcr_sitescan.h): everything ScanLevels accumulates is an integer.  A pair's
+// value and weight do not depend on the other pairs, a skipped pair is never an included one, and int32 and int64 sums do not
+// depend on order; the value written is one conversion and one multiply of such a sum.  So every output is the same bits whatever
+// the launch shape, the site order, the storm order and the chunking.  That is what the half-weights are for: a sum of fp64 hours
+// would depend on its order, and on the chunking once it crosses storms.
 
 namespace {
 
+constexpr int kScanMaxLevel = 8;            // level accumulators of a ScanLevels mode
 constexpr int kDuMaxLevel = kScanMaxLevel;
 
 // a footprint record as the duration scan reads it: the terms WfRec::uniform loads, and hw as the integer k_wind_prep stored
@@ -40,12 +54,66 @@ struct DuRec {
 static_assert(sizeof(DuRec) == sizeof(WfRec) && offsetof(DuRec, hw) == offsetof(WfRec, hw) && offsetof(DuRec, bn) == offsetof(WfRec, bn),
               "DuRec is WfRec's layout");
 
-// the policy of k_site_scan<DurationScan<UNIT_C, NL>>: the kLevels variant with NL accumulators (the call's n_level <= NL)
+// the mode of DurationScan (header comment); cells [n_level][n_hbin + 1][64] of int32: the storms of this lane whose hours at the
+// level pass exactly k thresholds
+template <int NL>
+struct ScanLevels {
+    static_assert(NL >= 1 && NL <= kScanMaxLevel, "a level mode has 1 to kScanMaxLevel level accumulators");
+    struct Storm {
+        int32_t lv[NL] = {};                // the weights of the records that reach each level,
+        int32_t lv_in = 0;                  // and of every included record
+    };
+    int64_t lv_total[NL] = {};              // this site's sums of the chunk's storms, per level
+    static ScanShape shape(int32_t n_level, int32_t n_hbin, const double *thr)
+    {
+        return ScanShape{n_level * n_hbin, sizeof(int32_t) * 64 * (size_t)n_level * (n_hbin + 1), n_hbin, thr};
+    }
+    template <class P> __device__ __forceinline__ void begin(const P &pol, const ScanLane &c)
+    {
+        for (int k = 0; k < pol.n_level * (pol.n_hbin + 1); ++k) c.lds[k * 64 + c.lane] = 0;
+    }
+    template <class P, class Rec> __device__ __forceinline__ void add(const P &pol, Storm &st, const ScanSite &me, const Rec &p, double q)
+    {
+        const double v = pol.value(me, p, q);
+        const int32_t h = pol.weight(p);
+        st.lv_in += h;
+#pragma unroll
+        for (int l = 0; l < NL; ++l) st.lv[l] += v >= pol.level[l] ? h : 0;               // (a NaN reaches none)
+    }
+    // a plane and a rank per level; a storm without an included record counts nowhere
+    template <class P> __device__ __forceinline__ void end_storm(const P &pol, const ScanLane &c, const Storm &st, int64_t s, bool)
+    {
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            if (l < pol.n_level) {                      // (wave-uniform)
+                const double d = st.lv_in ? (double)st.lv[l] * pol.unit : NAN;
+                if (pol.site_level[l] && c.valid) pol.site_level[l][c.site * c.a.n_trk + s] = d;
+                if (st.lv_in) c.lds[(l * (pol.n_hbin + 1) + scan_rank(c.a.thr, pol.n_hbin, d)) * 64 + c.lane] += 1;
+                lv_total[l] += st.lv[l];
+            }
+        }
+    }
+    // at least b + 1 thresholds, per level; and the level's total
+    template <class P> __device__ __forceinline__ void end_chunk(const P &pol, const ScanLane &c)
+    {
+        if (!c.valid) return;
+        int32_t *out = c.a.part + (c.chunk * c.a.n_site + c.site) * c.a.n_cell;
+        for (int l = 0; l < pol.n_level; ++l) {
+            int32_t cl = 0;
+            for (int b = pol.n_hbin - 1; b >= 0; --b) { cl += c.lds[(l * (pol.n_hbin + 1) + b + 1) * 64 + c.lane]; out[l * pol.n_hbin + b] = cl; }
+        }
+#pragma unroll
+        for (int l = 0; l < NL; ++l)
+            if (l < pol.n_level) pol.level_part[(c.chunk * c.a.n_site + c.site) * pol.n_level + l] = lv_total[l];
+    }
+};
+
+// the policy of k_site_scan<DurationScan<UNIT_C, NL>>: NL accumulators (the call's n_level <= NL)
 template <bool UNIT_C, int NL>
 struct DurationScan {
     using Rec = DuRec;
+    using Mode = ScanLevels<NL>;
     static constexpr int kUnroll = 2;
-    static constexpr int kLevels = NL;
     WindScan<UNIT_C> wind;
     double level[NL];                       // ascending; +inf past n_level
     double unit;                            // u: hours per half-weight
@@ -92,12 +160,10 @@ struct DuCall {
 };
 
 template <bool UNIT_C, int NL>
-hipError_t duration_launch(const DuCall &d, const ScanArgs<WfRec> &m, void *stage, dim3 grid, hipStream_t st)
+hipError_t duration_launch(const DuCall &d, const ScanRows<WfRec> &rows, const ScanLaunch &L, void *stage)
 {
-    const tcr_wind_tracks *t = d.t;
-    const double c = d.prm->ck_cd;
     DurationScan<UNIT_C, NL> pol{};
-    pol.wind = WindScan<UNIT_C>{c, 2.0 - c, 1.0 / (2.0 - c)};
+    pol.wind = wind_scan<UNIT_C>(d.prm);
     for (int l = 0; l < NL; ++l) {
         pol.level[l] = l < d.n_level ? d.levels[l] : INFINITY;
         pol.site_level[l] = (d.site_hours && l < d.n_level) ? d.site_hours[l] : nullptr;
@@ -105,18 +171,7 @@ hipError_t duration_launch(const DuCall &d, const ScanArgs<WfRec> &m, void *stag
     pol.unit = d.prm->dt_s / (7200.0 * d.prm->substeps);
     pol.n_level = d.n_level; pol.n_hbin = d.n_bin;
     pol.level_part = d.level_part;
-    // the footprint's rows under the duration's view of a record
-    ScanArgs<DuRec> v{};
-    v.rows = ScanRows<DuRec>{reinterpret_cast<DuRec *>(m.rows.rec), m.rows.seg, m.rows.storm, m.rows.cnt, m.rows.n_seg_max};
-    v.chunks = m.chunks; v.site_lon = m.site_lon; v.site_lat = m.site_lat;
-    v.n_site = m.n_site; v.n_tile = m.n_tile; v.n_trk = m.n_trk;
-    v.a_R = m.a_R; v.r_ang = m.r_ang; v.n_bin = m.n_bin;
-    for (int b = 0; b < kHzMaxBin; ++b) v.thr[b] = m.thr[b];
-    v.part = m.part; v.site_max = nullptr; v.pairs = m.pairs;
-    WfPrepArgs p{t->lon, t->lat, t->v, t->u250, t->v250, t->u850, t->v850, t->rmax_km, t->n_trk, t->n_t, t->row_stride,
-                 d.prm->dt_s, d.prm->rmax_const_km, d.prm->substeps, static_cast<WfStage *>(stage), m.rows};
-    const size_t lds = sizeof(int32_t) * 64 * (size_t)d.n_level * (d.n_bin + 1);         // (the scan zeroes n_level (n_bin + 1) rows)
-    return scan_launch(k_wind_prep, p, t->n_trk, v, grid, lds, st, pol);
+    return wind_scan_launch(d.t, d.prm, rows, L, stage, pol);         // (the scan sees the footprint's rows as DuRec)
 }
 
 }  // namespace
@@ -130,31 +185,27 @@ int tcr_duration_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_para
     hipStream_t st = enter(ctx, stream_);
     if (!st || duration_check(ctx, t, prm, n_site, site_lon, site_lat, n_level, levels, n_bin, thresholds, counts)) return -1;
     ScanWs &w = ctx->an.du;
-    const int64_t n_tile = (n_site + 63) / 64;
-    std::vector<int64_t> tab, gch;
-    scan_chunks(t, n_tile, tab, gch);                   // scan_run's own table: the size of the totals' workspace
-    const int64_t n_chunk = (int64_t)tab.size() / 3;
-    if (w.d[6].grow(ctx, sizeof(int64_t) * (size_t)std::max<int64_t>(1, n_chunk * n_site * n_level)) < 0) return -1;
-    int64_t *level_part = reinterpret_cast<int64_t *>(w.d[6].p);
+    const ScanPlan plan = scan_plan(t, n_site, kScanAnyChunk);
+    if (w.d[kWsOwn0].grow(ctx, sizeof(int64_t) * (size_t)std::max<int64_t>(1, plan.n_chunk * n_site * n_level)) < 0) return -1;
+    int64_t *level_part = reinterpret_cast<int64_t *>(w.d[kWsOwn0].p);
     const int64_t n_rec = (t->n_t - 1) * prm->substeps + 1;
     const size_t n_stage = (size_t)std::max<int64_t>(1, t->n_trk * t->n_t);
-    double thr[kHzMaxBin] = {};                         // the n_bin thresholds; the scan is handed n_level n_bin >= n_bin of these
-    for (int b = 0; b < n_bin; ++b) thr[b] = thresholds[b];
     const DuCall d{t, prm, n_level, n_bin, levels, site_hours, level_part};
-    const int rc = scan_run<WfRec>(ctx, w, "tcr_duration", t, n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat, prm->r_out_km,
-                                   kWfEarthR / 1000.0, n_level * n_bin, thr, counts, nullptr, st,
-                                   [&](const ScanArgs<WfRec> &m, void *stage, dim3 grid, size_t) {
+    // (the modes of every NL have the one shape)
+    const int rc = scan_run<WfRec>(ctx, w, "tcr_duration", t, plan, ScanLevels<kDuMaxLevel>::shape(n_level, n_bin, thresholds), n_rec,
+                                   n_stage * sizeof(WfStage), n_site, site_lon, site_lat, prm->r_out_km, kWfEarthR / 1000.0, counts, nullptr,
+                                   st, [&](const ScanRows<WfRec> &rows, const ScanLaunch &L, void *stage) {
         const bool unit = prm->ck_cd == 1.0, few = n_level <= 4;
-        if (unit && few) return duration_launch<true, 4>(d, m, stage, grid, st);
-        if (unit) return duration_launch<true, kDuMaxLevel>(d, m, stage, grid, st);
-        if (few) return duration_launch<false, 4>(d, m, stage, grid, st);
-        return duration_launch<false, kDuMaxLevel>(d, m, stage, grid, st);
+        if (unit && few) return duration_launch<true, 4>(d, rows, L, stage);
+        if (unit) return duration_launch<true, kDuMaxLevel>(d, rows, L, stage);
+        if (few) return duration_launch<false, 4>(d, rows, L, stage);
+        return duration_launch<false, kDuMaxLevel>(d, rows, L, stage);
     });
     if (rc) return rc;
     if (half_steps) {
         const int64_t n_out = n_site * t->n_group * n_level;
         hipLaunchKernelGGL(k_duration_reduce, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, level_part,
-                           reinterpret_cast<const int64_t *>(w.d[4].p) + tab.size(), n_site, t->n_group, n_level, half_steps);
+                           scan_dev_tab(w) + plan.tab.size(), n_site, t->n_group, n_level, half_steps);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipEventRecord(w.done, st));
     }

@@ -38,6 +38,7 @@ struct HzSample {                           // one live sample (64 bytes)
 
 struct HazardScan {
     using Rec = HzSample;
+    using Mode = ScanPeak<false>;
     static constexpr int kUnroll = 4;
     __device__ __forceinline__ double value(const ScanSite &, const HzSample &p, double) const { return p.v; }
 };
@@ -102,10 +103,11 @@ int tcr_hazard_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, int64_t n_site, con
 {
     hipStream_t st = enter(ctx, stream_);
     if (!st || hazard_check(ctx, t, n_site, site_lon, site_lat, radius_km, n_bin, thresholds, counts)) return -1;
-    return scan_run<HzSample>(ctx, ctx->an.hz, "tcr_hazard", t, t->n_t, 0, n_site, site_lon, site_lat, radius_km, kHzRe, n_bin, thresholds,
-                              counts, site_max, st, [&](const ScanArgs<HzSample> &m, void *, dim3 grid, size_t lds) {
-        HzPrepArgs p{t->lon, t->lat, t->vmax, t->n_trk, t->n_t, t->row_stride, m.rows};
-        return scan_launch(k_hazard_prep, p, t->n_trk, m, grid, lds, st, HazardScan{});
+    return scan_run<HzSample>(ctx, ctx->an.hz, "tcr_hazard", t, scan_plan(t, n_site, kScanAnyChunk),
+                              HazardScan::Mode::shape(n_bin, thresholds), t->n_t, 0, n_site, site_lon, site_lat, radius_km, kHzRe, counts,
+                              site_max, st, [&](const ScanRows<HzSample> &rows, const ScanLaunch &L, void *) {
+        HzPrepArgs p{t->lon, t->lat, t->vmax, t->n_trk, t->n_t, t->row_stride, rows};
+        return scan_launch(k_hazard_prep, p, rows, L, HazardScan{});
     });
 }
 

@@ -9,9 +9,12 @@
 //
 // A user of the site scan (tcr_sitescan.h) with the footprint's own prep kernel, record and value (k_wind_prep, WfRec, WindScan of
 // tcr_windfield.hip).  What is the loss's own:
-//   LossScan<c == 1>  WindScan plus kLoss: the compile-time loss variant of k_site_scan.  A lane holds value and
-//                     1 / (v_half_i - v_thresh) of its site next to the site's terms; once a storm's m is known it computes its
-//                     loss, adds it to its running site sum, and the wave's butterfly sum goes to tile_loss[tile][storm];
+//   LossScan<c == 1>  WindScan with the loss's parameters and buffers, and LossMode for its mode;
+//   LossMode          the scan's peak mode plus the loss.  A lane holds value and 1 / (v_half_i - v_thresh) of its site over the
+//                     chunk; once a storm's m is known it computes its loss and adds it to its running sum of the chunk's storms
+//                     (storm order), which goes to site_part [n_chunk][n_site]; per storm the wave sums its 64 lane losses with a
+//                     fixed butterfly and lane 0 stores the sum to tile_loss [n_tile][n_trk] (a storm culled for the whole tile: 0,
+//                     without the butterfly);
 //   k_loss_events     one thread per storm: event_loss[s] = tile_loss[0][s] + tile_loss[1][s] + ... (coalesced: [tile][storm]);
 //   k_loss_years      one wave per group: lane j sums every 64th storm of the group from the j-th on, then the butterfly; the maximum
 //                     likewise (a max does not depend on the order);
@@ -25,9 +28,37 @@ namespace {
 
 struct LossTerms { double value, inv; };    // exposed value (0: contributes nothing) and 1 / (v_half - v_thresh) of a lane's site
 
+// the mode of LossScan: ScanPeak<false> (the footprint's counts), with the loss between the storm's peak and its count
+struct LossMode : ScanPeak<false> {
+    LossTerms terms;                        // of this lane's site
+    double loss_acc = 0.0;                  // this site's losses of the chunk's storms, summed in storm order
+    template <class P> __device__ __forceinline__ void begin(const P &pol, const ScanLane &c)
+    {
+        ScanPeak<false>::begin(pol, c);
+        terms = pol.site_terms(c.my, c.valid);
+    }
+    template <class P> __device__ __forceinline__ void end_storm(const P &pol, const ScanLane &c, const Storm &st, int64_t s, bool near)
+    {
+        store(c, s, st.m);
+        double t = 0.0;                                 // a storm culled for the whole tile: 0, without the butterfly
+        if (near) {
+            const double l = pol.loss(terms, st.m);
+            loss_acc += l;
+            t = wave_sum(l);
+        }
+        if (c.lane == 0) pol.tile_loss[c.tile * c.a.n_trk + s] = t;
+        count(c, st.m);
+    }
+    template <class P> __device__ __forceinline__ void end_chunk(const P &pol, const ScanLane &c)
+    {
+        ScanPeak<false>::end_chunk(pol, c);
+        if (c.valid) pol.site_part[c.chunk * c.a.n_site + c.site] = loss_acc;
+    }
+};
+
 template <bool UNIT_C>
 struct LossScan : WindScan<UNIT_C> {
-    static constexpr bool kLoss = true;
+    using Mode = LossMode;
     const double *site_value, *site_v_half; // [n_site]; site_v_half NULL: v_half0 everywhere
     double v_thresh, v_half0;
     double *tile_loss;                      // [n_tile][n_trk]
@@ -106,41 +137,36 @@ int tcr_loss_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params *
                  const double *thresholds, int32_t *counts, double *event_loss, double *year_agg, double *year_max, double *site_loss,
                  void *stream_)
 {
-    if (!ctx) return -1;
-    if (loss_check(ctx, t, prm, lp, n_site, site_lon, site_lat, site_value, n_bin, thresholds, counts, event_loss, year_agg, year_max,
-                   site_loss))
+    hipStream_t st = enter(ctx, stream_);
+    if (!st || loss_check(ctx, t, prm, lp, n_site, site_lon, site_lat, site_value, n_bin, thresholds, counts, event_loss, year_agg,
+                          year_max, site_loss))
         return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : ctx->stream;
     ScanWs &w = ctx->an.ls;
-    const int64_t n_trk = t->n_trk, n_tile = (n_site + 63) / 64;
-    std::vector<int64_t> tab, gch;
-    scan_chunks(t, n_tile, tab, gch);                   // scan_run's own table: the sizes of the two loss workspaces
-    const int64_t n_chunk = (int64_t)tab.size() / 3;
+    const ScanPlan plan = scan_plan(t, n_site, kScanAnyChunk);
+    const int64_t n_trk = t->n_trk, n_tile = plan.n_tile, n_chunk = plan.n_chunk;
     if (n_tile * std::max<int64_t>(1, n_trk) >= ((int64_t)1 << 40) ||
-        w.d[6].grow(ctx, sizeof(double) * (size_t)std::max<int64_t>(1, n_tile * n_trk)) < 0 ||
-        w.d[7].grow(ctx, sizeof(double) * (size_t)std::max<int64_t>(1, n_chunk * n_site)) < 0) {
+        w.d[kWsOwn0].grow(ctx, sizeof(double) * (size_t)std::max<int64_t>(1, n_tile * n_trk)) < 0 ||
+        w.d[kWsOwn1].grow(ctx, sizeof(double) * (size_t)std::max<int64_t>(1, n_chunk * n_site)) < 0) {
         (void)hipGetLastError();
         return fail(ctx, "tcr_loss: the tile-loss workspace (sites / 64 x storms doubles) does not fit; split the sites");
     }
-    double *tile_loss = reinterpret_cast<double *>(w.d[6].p), *site_part = reinterpret_cast<double *>(w.d[7].p);
+    double *tile_loss = reinterpret_cast<double *>(w.d[kWsOwn0].p), *site_part = reinterpret_cast<double *>(w.d[kWsOwn1].p);
     const int64_t n_rec = (t->n_t - 1) * prm->substeps + 1;
     const size_t n_stage = (size_t)std::max<int64_t>(1, n_trk * t->n_t);
-    const double c = prm->ck_cd;
-    const int rc = scan_run<WfRec>(ctx, w, "tcr_loss", t, n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat, prm->r_out_km,
-                                   kWfEarthR / 1000.0, n_bin, thresholds, counts, nullptr, st,
-                                   [&](const ScanArgs<WfRec> &m, void *stage, dim3 grid, size_t lds) {
-        if (c == 1.0)
-            return wind_scan_launch(t, prm, m, stage, grid, lds, st,
-                                    LossScan<true>{{c, 2.0 - c, 1.0 / (2.0 - c)}, site_value, site_v_half, lp->v_thresh, lp->v_half, tile_loss, site_part});
-        return wind_scan_launch(t, prm, m, stage, grid, lds, st,
-                                LossScan<false>{{c, 2.0 - c, 1.0 / (2.0 - c)}, site_value, site_v_half, lp->v_thresh, lp->v_half, tile_loss, site_part});
+    const int rc = scan_run<WfRec>(ctx, w, "tcr_loss", t, plan, LossMode::shape(n_bin, thresholds), n_rec, n_stage * sizeof(WfStage), n_site,
+                                   site_lon, site_lat, prm->r_out_km, kWfEarthR / 1000.0, counts, nullptr, st,
+                                   [&](const ScanRows<WfRec> &rows, const ScanLaunch &L, void *stage) {
+        if (prm->ck_cd == 1.0)
+            return wind_scan_launch(t, prm, rows, L, stage,
+                                    LossScan<true>{wind_scan<true>(prm), site_value, site_v_half, lp->v_thresh, lp->v_half, tile_loss, site_part});
+        return wind_scan_launch(t, prm, rows, L, stage,
+                                LossScan<false>{wind_scan<false>(prm), site_value, site_v_half, lp->v_thresh, lp->v_half, tile_loss, site_part});
     });
     if (rc) return rc;
-    const int64_t *d_tab = reinterpret_cast<const int64_t *>(w.d[4].p);
+    const int64_t *d_tab = scan_dev_tab(w);
     if (n_trk > 0)
         hipLaunchKernelGGL(k_loss_events, dim3((unsigned)((n_trk + 255) / 256)), dim3(256), 0, st, tile_loss, n_tile, n_trk, event_loss);
-    hipLaunchKernelGGL(k_loss_years, dim3((unsigned)t->n_group), dim3(64), 0, st, event_loss, d_tab, d_tab + tab.size(), year_agg,
+    hipLaunchKernelGGL(k_loss_years, dim3((unsigned)t->n_group), dim3(64), 0, st, event_loss, d_tab, d_tab + plan.tab.size(), year_agg,
                        year_max);
     hipLaunchKernelGGL(k_loss_sites, dim3((unsigned)((n_site + 255) / 256)), dim3(256), 0, st, site_part, n_chunk, n_site, site_loss);
     HIPCHK(ctx, hipGetLastError());
@@ -152,9 +178,8 @@ int tcr_loss_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params 
                   const double *site_lon, const double *site_lat, const double *site_value, const double *site_v_half, int32_t n_bin,
                   const double *thresholds, int32_t *counts, double *event_loss, double *year_agg, double *year_max, double *site_loss)
 {
-    if (!ctx) return -1;
-    if (loss_check(ctx, t, prm, lp, n_site, site_lon, site_lat, site_value, n_bin, thresholds, counts, event_loss, year_agg, year_max,
-                   site_loss))
+    if (!enter(ctx) || loss_check(ctx, t, prm, lp, n_site, site_lon, site_lat, site_value, n_bin, thresholds, counts, event_loss, year_agg,
+                                  year_max, site_loss))
         return -1;
     // what the device entry point cannot report
     for (int64_t i = 0; i < n_site; ++i) {
@@ -162,7 +187,6 @@ int tcr_loss_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params 
         if (site_v_half && !(std::isfinite(site_v_half[i]) && site_v_half[i] > lp->v_thresh))
             return fail(ctx, "tcr_loss_host: site_v_half must be finite and > v_thresh at every site");
     }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf B;
     tcr_wind_tracks d;
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, n_bin, false);

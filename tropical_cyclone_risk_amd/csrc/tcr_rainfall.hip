@@ -12,12 +12,13 @@
 //                    already in mm/h (T0, the inner slope (Tm - T0) / rm, Tm, rm, 1 / re) and the trapezoid weight w (hours).
 //                    The three planes are read where they lie: a record needs two neighbouring samples of them and nothing
 //                    derived per sample, so there is no stage buffer;
-//   RainScan<SUM>    the policy of k_site_scan.  SUM: kSum, the scan adds w rate in record order; otherwise the scan's max of rate.
+//   RainScan<SUM>    the policy of k_site_scan, with ScanPeak<SUM> for its mode.  SUM: the scan adds w rate in record order;
+//                    otherwise the scan's max of rate.
 //
 // Per included pair:  r = 2 R asin(sqrt(a)),  rate = max(0, r < rm ? T0 + slope r : Tm exp(-(r - rm) / re)): one asin, one sqrt and
 // either a multiply-add or one exp.
 //
-// Bit-identity: tcr_sitescan.h's argument for kSum.  The sum of a (site, storm) is one lane's, over the records with a <= a_out in
+// Bit-identity: tcr_sitescan.h's argument for a sum in record order.  The sum of a (site, storm) is one lane's, over the records with a <= a_out in
 // record order, whatever is culled around them; nothing here or there reduces site_value across lanes or chunks.
 
 namespace {
@@ -98,8 +99,8 @@ __global__ __launch_bounds__(64) void k_rain_prep(RfPrepArgs a)
 template <bool SUM>
 struct RainScan {
     using Rec = RfRec;
+    using Mode = ScanPeak<SUM>;
     static constexpr int kUnroll = 2;
-    static constexpr bool kSum = SUM;
     __device__ __forceinline__ double value(const ScanSite &s, const RfRec &p, double q) const { return at_angle(s, p, scan_pair_angle(q)); }
     // the same from the pair's angle (radians), which a joint scan (tcr_compound.hip) forms once for two hazards
     __device__ __forceinline__ double at_angle(const ScanSite &, const RfRec &p, double ang) const
@@ -109,6 +110,14 @@ struct RainScan {
         return SUM ? p.w * rate : rate;
     }
 };
+
+// the prep kernel's arguments of a call; rows: where the records go
+inline RfPrepArgs rain_prep_args(const tcr_hazard_tracks *t, const tcr_rain_params *prm, const ScanRows<RfRec> &rows)
+{
+    return RfPrepArgs{t->lon, t->lat, t->vmax, t->n_trk, t->n_t, t->row_stride, prm->dt_s / (3600.0 * prm->substeps), prm->v_lo_kt,
+                      prm->v_hi_kt, {prm->a[0], prm->a[1], prm->a[2], prm->a[3]}, {prm->b[0], prm->b[1], prm->b[2], prm->b[3]},
+                      prm->substeps, rows};
+}
 
 // U of a clamp end (knots)
 inline double rf_u(double kt) { return 1.0 + (kt - 35.0) / 33.0; }
@@ -147,13 +156,13 @@ int tcr_rainfall_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, const tcr_rain_pa
     hipStream_t st = enter(ctx, stream_);
     if (!st || rainfall_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
     const int64_t n_rec = (t->n_t - 1) * prm->substeps + 1;
-    return scan_run<RfRec>(ctx, ctx->an.rf, "tcr_rainfall", t, n_rec, 0, n_site, site_lon, site_lat, prm->r_out_km, kWfEarthR / 1000.0,
-                           n_bin, thresholds, counts, site_value, st, [&](const ScanArgs<RfRec> &m, void *, dim3 grid, size_t lds) {
-        RfPrepArgs p{t->lon, t->lat, t->vmax, t->n_trk, t->n_t, t->row_stride, prm->dt_s / (3600.0 * prm->substeps), prm->v_lo_kt,
-                     prm->v_hi_kt, {prm->a[0], prm->a[1], prm->a[2], prm->a[3]}, {prm->b[0], prm->b[1], prm->b[2], prm->b[3]},
-                     prm->substeps, m.rows};
-        if (prm->stat == TCR_RAIN_TOTAL) return scan_launch(k_rain_prep, p, t->n_trk, m, grid, lds, st, RainScan<true>{});
-        return scan_launch(k_rain_prep, p, t->n_trk, m, grid, lds, st, RainScan<false>{});
+    // (both stats' modes have the one shape)
+    return scan_run<RfRec>(ctx, ctx->an.rf, "tcr_rainfall", t, scan_plan(t, n_site, kScanAnyChunk), ScanPeak<true>::shape(n_bin, thresholds),
+                           n_rec, 0, n_site, site_lon, site_lat, prm->r_out_km, kWfEarthR / 1000.0, counts, site_value, st,
+                           [&](const ScanRows<RfRec> &rows, const ScanLaunch &L, void *) {
+        const RfPrepArgs p = rain_prep_args(t, prm, rows);
+        if (prm->stat == TCR_RAIN_TOTAL) return scan_launch(k_rain_prep, p, rows, L, RainScan<true>{});
+        return scan_launch(k_rain_prep, p, rows, L, RainScan<false>{});
     });
 }
 

@@ -175,6 +175,7 @@ __global__ __launch_bounds__(64) void k_wind_prep(WfPrepArgs a)
 template <bool UNIT_C>
 struct WindScan {
     using Rec = WfRec;
+    using Mode = ScanPeak<false>;
     static constexpr int kUnroll = 2;
     double c, two_c, inv_exp;               // profile: c, 2 - c, 1 / (2 - c)
     __device__ __forceinline__ double value(const ScanSite &s, const WfRec &p, double q) const { return at_angle(s, p, scan_pair_angle(q)); }
@@ -214,14 +215,24 @@ int windfield_check(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_param
     return scan_check(ctx, who, t, 1 << 20, "1 <= n_t <= 2^20", n_site, n_bin, thr);
 }
 
-// The launch step of scan_run for every analysis on the footprint's records: the footprint's prep kernel, then Policy's scan.
-template <typename Policy>
-hipError_t wind_scan_launch(const tcr_wind_tracks *t, const tcr_wind_params *prm, const ScanArgs<WfRec> &m, void *stage, dim3 grid,
-                            size_t lds, hipStream_t st, const Policy &pol)
+// the prep kernel's arguments of a call: stage is the [n_trk][n_t] workspace, rows where the records go
+inline WfPrepArgs wind_prep_args(const tcr_wind_tracks *t, const tcr_wind_params *prm, void *stage, const ScanRows<WfRec> &rows)
 {
-    WfPrepArgs p{t->lon, t->lat, t->v, t->u250, t->v250, t->u850, t->v850, t->rmax_km, t->n_trk, t->n_t, t->row_stride,
-                 prm->dt_s, prm->rmax_const_km, prm->substeps, static_cast<WfStage *>(stage), m.rows};
-    return scan_launch(k_wind_prep, p, t->n_trk, m, grid, lds, st, pol);
+    return WfPrepArgs{t->lon, t->lat, t->v, t->u250, t->v250, t->u850, t->v850, t->rmax_km, t->n_trk, t->n_t, t->row_stride,
+                      prm->dt_s, prm->rmax_const_km, prm->substeps, static_cast<WfStage *>(stage), rows};
+}
+
+// the profile parameters of WindScan<c == 1> from ck_cd
+template <bool UNIT_C>
+WindScan<UNIT_C> wind_scan(const tcr_wind_params *prm) { return WindScan<UNIT_C>{prm->ck_cd, 2.0 - prm->ck_cd, 1.0 / (2.0 - prm->ck_cd)}; }
+
+// The launch step of scan_run for every analysis on the footprint's records: the footprint's prep kernel, then Policy's scan, which
+// may read the rows through a record type of its own with WfRec's layout.
+template <typename Policy>
+hipError_t wind_scan_launch(const tcr_wind_tracks *t, const tcr_wind_params *prm, const ScanRows<WfRec> &rows, const ScanLaunch &L,
+                            void *stage, const Policy &pol)
+{
+    return scan_launch(k_wind_prep, wind_prep_args(t, prm, stage, rows), rows.template as<typename Policy::Rec>(), L, pol);
 }
 
 // What a _host entry point checks and a _dev one cannot report: the rmax_km plane (when given) is finite and > 0 at every sample
@@ -268,12 +279,12 @@ int tcr_windfield_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_par
     if (!st || windfield_check(ctx, t, prm, n_site, site_lon, site_lat, n_bin, thresholds, counts)) return -1;
     const int64_t n_rec = (t->n_t - 1) * prm->substeps + 1;
     const size_t n_stage = (size_t)std::max<int64_t>(1, t->n_trk * t->n_t);
-    const double c = prm->ck_cd;
-    return scan_run<WfRec>(ctx, ctx->an.wf, "tcr_windfield", t, n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat, prm->r_out_km,
-                           kWfEarthR / 1000.0, n_bin, thresholds, counts, site_max, st,
-                           [&](const ScanArgs<WfRec> &m, void *stage, dim3 grid, size_t lds) {
-        if (c == 1.0) return wind_scan_launch(t, prm, m, stage, grid, lds, st, WindScan<true>{c, 2.0 - c, 1.0 / (2.0 - c)});
-        return wind_scan_launch(t, prm, m, stage, grid, lds, st, WindScan<false>{c, 2.0 - c, 1.0 / (2.0 - c)});
+    return scan_run<WfRec>(ctx, ctx->an.wf, "tcr_windfield", t, scan_plan(t, n_site, kScanAnyChunk),
+                           ScanPeak<false>::shape(n_bin, thresholds), n_rec, n_stage * sizeof(WfStage), n_site, site_lon, site_lat,
+                           prm->r_out_km, kWfEarthR / 1000.0, counts, site_max, st,
+                           [&](const ScanRows<WfRec> &rows, const ScanLaunch &L, void *stage) {
+        if (prm->ck_cd == 1.0) return wind_scan_launch(t, prm, rows, L, stage, wind_scan<true>(prm));
+        return wind_scan_launch(t, prm, rows, L, stage, wind_scan<false>(prm));
     });
 }
 
