@@ -905,6 +905,41 @@ int tcr_tail_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col
 int tcr_tail_host(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, int32_t k, double total_years,
                   int32_t n_period, const double *periods, double *param, double *level, int32_t *n_valid);
 
+/* ---- row packing (event footprints): the entries of every row of a per-storm plane at or above a floor, as CSR ------------- */
+/* replaces: nothing in the reference's code.  Every site analysis above answers a question per site, summed over storms; this is
+ * the event set itself: which storm put how much wind or rain on which site, for the block of sites whose plane is on the device.
+ *   plane           [n_row][row_stride] fp64, of which the first n_col values of a row are the row.
+ *   kept            entry (r, c) is kept iff plane[r][c] >= min_value as an IEEE comparison, the comparison of `counts`
+ *                   (site_max >= thresholds[b]): a NaN of either sign is never kept, -0.0 >= 0.0 is true, and min_value = -inf
+ *                   keeps every value that is not NaN.
+ *   row_ptr         [n_row + 1] int64: row_ptr[0] = 0, row_ptr[r + 1] - row_ptr[r] the number of kept entries of row r,
+ *                   row_ptr[n_row] their number nnz.
+ *   col, val        [nnz] int32 and fp64: the kept entries of row r in ascending column order at positions row_ptr[r] ...; val is
+ *                   a bit copy (no arithmetic touches a value: a kept -0.0 stays -0.0).
+ * The result is a function of the plane and min_value alone: bit-identical from run to run and whatever the launch shape (a
+ * position is computed from ballots and sums, never handed out by an atomic).
+ * Arguments: tcr_select's rules for the plane (n_row >= 0, 1 <= n_col <= 2^31 - 1, row_stride >= n_col); min_value must not be
+ * NaN; capacity >= 0.  Every message begins with "tcr_rowpack:" and nothing is launched after one.  n_row == 0 writes
+ * row_ptr[0] = 0 and returns 0.
+ *   tcr_rowpack_count_dev   writes row_ptr (one workgroup per row counts, one workgroup sums in place).  Counting is a call of
+ *                           its own because the caller sizes col / val from row_ptr[n_row] between the two: the one host read
+ *                           of the pass.
+ *   tcr_rowpack_fill_dev    writes col and val of the first `capacity` entries from the row_ptr the count gave.  It never writes
+ *                           at or past capacity, whatever row_ptr says: an entry whose position is not in [0, capacity) is
+ *                           dropped.  It cannot report that; it guarantees the bound, and that the first capacity entries are
+ *                           the right ones.  capacity == 0: col and val may be NULL.
+ *   tcr_rowpack_host        everything in host memory.  capacity == 0 and col == val == NULL: counts only.  Otherwise it fills
+ *                           row_ptr and then fails ("capacity") when nnz > capacity, with col / val untouched.
+ * _dev: plane, row_ptr, col and val are device memory, asynchronous on `stream`.  No workspace (the scan works in row_ptr itself):
+ * calls on one context need no ordering.  A turn of a row's workgroup covers 256 x TCR_ROWPACK_UNROLL columns. */
+#define TCR_ROWPACK_UNROLL 8          /* loads a lane has in flight: a workgroup of 256 threads takes 2048 columns per turn */
+int tcr_rowpack_count_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, double min_value,
+                          int64_t *row_ptr, void *stream);
+int tcr_rowpack_fill_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, double min_value,
+                         const int64_t *row_ptr, int64_t capacity, int32_t *col, double *val, void *stream);
+int tcr_rowpack_host(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, double min_value,
+                     int64_t *row_ptr, int64_t capacity, int32_t *col, double *val);
+
 #ifdef __cplusplus
 }
 #endif

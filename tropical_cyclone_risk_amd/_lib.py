@@ -17,6 +17,7 @@ FLAG_IS_TC, FLAG_ACCEPTED = 1, 2
 RAIN_TOTAL, RAIN_PEAK_RATE = 0, 1        # TCR_RAIN_*: tcr_rain_params.stat
 SELECT_LDS_KEYS, SELECT_MAX_RANKS = 8192, 64     # TCR_SELECT_*: keys of a row tcr_select_* selects in LDS, ranks of one call
 TAIL_MAX_K = 2048                 # TCR_TAIL_MAX_K: exceedances of a row tcr_tail_* fits
+ROWPACK_UNROLL = 8                # TCR_ROWPACK_UNROLL: a workgroup of tcr_rowpack_* takes 256 x this many columns of a row per turn
 STAGES = ('start', 'seed', 'select', 'order', 'gather', 'fourier', 'integrate', 'screen', 'select_tc', 'dense', 'emit', 'flags', 'stats', 'pack')
 STATIC_MODES = ('f64', 'f64_split', 'pack16', 'u8_f32', 'pack64')     # StaticMode (tcr_static_info)
 N_STATS = 10        # TCR_N_STATS: words of a tcr_stats_dev / tcr_round.stats counter block
@@ -43,7 +44,7 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_landfall_host', 'tcr_climatology_dev', 'tcr_climatology_host', 'tcr_windfield_dev', 'tcr_windfield_host',
            'tcr_windfield_pairs', 'tcr_loss_dev', 'tcr_loss_host', 'tcr_rainfall_dev', 'tcr_rainfall_host', 'tcr_rainfall_pairs',
            'tcr_compound_dev', 'tcr_compound_host', 'tcr_compound_pairs', 'tcr_duration_dev', 'tcr_duration_host', 'tcr_duration_pairs',
-           'tcr_select_dev', 'tcr_select_host', 'tcr_tail_dev', 'tcr_tail_host',
+           'tcr_select_dev', 'tcr_select_host', 'tcr_tail_dev', 'tcr_tail_host', 'tcr_rowpack_count_dev', 'tcr_rowpack_fill_dev', 'tcr_rowpack_host',
            'tcr_probe_rhs_f32_host', 'tcr_integrate_steps_host', 'tcr_integrate_steps_f32_host')
 TCR_COMM_ID_BYTES = 128
 
@@ -312,6 +313,10 @@ def lib():
     L.tcr_select_host.argtypes = L.tcr_select_dev.argtypes[:-1]
     L.tcr_tail_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int32, DP] + [C.c_void_p] * 4
     L.tcr_tail_host.argtypes = L.tcr_tail_dev.argtypes[:-1]
+    L.tcr_rowpack_count_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]
+    L.tcr_rowpack_fill_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tcr_rowpack_host.argtypes = L.tcr_rowpack_fill_dev.argtypes[:-1]
     if L.tcr_abi_version() != TCR_ABI_VERSION:
         raise TcrError('libtcrisk_hip.so ABI version %d != binding version %d'
                        % (L.tcr_abi_version(), TCR_ABI_VERSION))

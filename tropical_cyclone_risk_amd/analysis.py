@@ -274,6 +274,31 @@ def check_return_period_args(p, a):
         p.error('--tail-exceedances needs --return-periods')
 
 
+def parse_floor(text):
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--events-min: expected a number, got %r' % text)
+    if v != v:
+        raise argparse.ArgumentTypeError('--events-min: the floor must not be NaN')
+    return v
+
+
+def add_events_arg(p, what):
+    p.add_argument('--events-out', default=None, metavar='FILE.npz',
+                   help='also write the event table: per site, the storms whose %s is at or above --events-min, with that value '
+                        '(events.site_event_table; a pass of its own)' % what)
+    p.add_argument('--events-min', type=parse_floor, default=None, metavar='V', help='the floor of --events-out (required with it)')
+
+
+def check_events_args(p, a):
+    """What the options of add_events_arg ask of each other, after parsing."""
+    if a.events_out is not None and a.events_min is None:
+        p.error('--events-out needs --events-min')
+    if a.events_min is not None and a.events_out is None:
+        p.error('--events-min needs --events-out')
+
+
 def read_sites_csv(fn):
     out = []
     for line in open(fn):

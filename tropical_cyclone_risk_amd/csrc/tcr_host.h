@@ -1,6 +1,6 @@
 // What the host side of libtcrisk_hip.so is written with: the error path, the owners of device and pinned memory, the per-call
 // bag of temporaries, the dispatch over the kernels' evaluation variants and the prologue of an entry point.  Every host file
-// behind the C ABI (tcr_stage.hip ... tcr_tail.hip; the list is tcr_abi.hip's) uses these and nothing else of its neighbours.
+// behind the C ABI (tcr_stage.hip ... tcr_rowpack.hip; the list is tcr_abi.hip's) uses these and nothing else of its neighbours.
 //
 // Invariants kept HERE, not by convention:
 //   epoch    every allocation of context memory goes through DevArray::grow, which bumps HostCtx::epoch.  A captured round

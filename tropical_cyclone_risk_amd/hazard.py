@@ -82,9 +82,11 @@ def parse_args(argv=None):
     p.add_argument('--radius-km', type=float, default=100.0)
     analysis.add_threshold_arg(p)
     analysis.add_return_period_arg(p, 'near-site intensity (m/s)')
+    analysis.add_events_arg(p, 'near-site intensity (m/s)')
     analysis.add_track_args(p, 'hazard.npz')
     a = p.parse_args(argv)
     analysis.check_return_period_args(p, a)
+    analysis.check_events_args(p, a)
     if not (a.site or a.sites or a.grid):
         p.error('give sites with --site, --sites or --grid')
     return a
@@ -115,6 +117,10 @@ def main(argv=None):
     analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp)
     if more:
         levels.print_return_levels(res, site_lon, site_lat)
+    if args.events_out is not None:
+        from . import events
+        events.write_cli_events(args, lambda t, x, y: site_hazard(t[0], t[1], t[2], groups, x, y, return_max=True, **kw),
+                                (lon, lat, vmax), site_lon, site_lat, 'site_max', 'm/s', groups, gfile, gyear)
     return 0
 
 

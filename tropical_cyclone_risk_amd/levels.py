@@ -139,6 +139,44 @@ def row_tail(plane, k, total_years, return_periods, engine=None, device=0):
 TAIL_KEYS = ('tail_level', 'tail_xi', 'tail_sigma', 'tail_threshold')      # what tail_exceedances adds to site_return_levels' dict
 
 
+def check_sites(site_lon, site_lat, max_bytes):
+    """(Flavour, site_lon, site_lat as fp64 [n_site] of it, max_bytes) of a blocked pass, or ValueError: before any scan."""
+    max_bytes = int(max_bytes)
+    if max_bytes < 1:
+        raise ValueError('max_bytes must be >= 1')
+    fl = analysis.Flavour(site_lon)
+    site_lon, site_lat = (fl.conv(a).reshape(-1) for a in (site_lon, site_lat))
+    n_site = int(site_lon.shape[0])
+    if int(site_lat.shape[0]) != n_site or n_site < 1:
+        raise ValueError('site_lon and site_lat must be non-empty and of one length')
+    if not bool(fl.xp.isfinite(site_lon).all()) or not bool(fl.xp.isfinite(site_lat).all()):
+        raise ValueError('site coordinates must be finite')
+    return fl, site_lon, site_lat, max_bytes
+
+
+def site_blocks(scan, fl, site_lon, site_lat, key, max_bytes, n_trk=None):
+    """The one block loop of the package (site_return_levels, events.site_event_table): the sites (check_sites') in spatial order
+    (sitescan.spatial_order), cut into runs of max(64, max_bytes // (8 n_trk)) sites rounded down to a multiple of 64; n_trk None: a
+    first block of 64 sites tells.  Yields (i, j, plane, res, order) per block: the block is the sites order[i:j], plane = res[key]
+    [j - i][n_trk] is the scan's per-storm plane of it (taken out of res), res the rest of the scan's dict.  The consumer drops the
+    plane before it asks for the next block."""
+    n_site = int(site_lon.shape[0])
+    order = spatial_order(site_lon, site_lat, fl.xp)
+    slon, slat = site_lon[order], site_lat[order]
+    block_of = lambda n: max(SITE_BLOCK, max_bytes // (8 * max(int(n), 1))) // SITE_BLOCK * SITE_BLOCK        # noqa: E731
+    block = SITE_BLOCK if n_trk is None else block_of(n_trk)
+    i = 0
+    while i < n_site:
+        j = min(i + block, n_site)
+        res = scan(slon[i:j], slat[i:j])
+        plane = res.pop(key)
+        if i == 0:
+            block = block_of(plane.shape[1])
+        yield i, j, plane, res, order
+        del plane, res
+        i = j
+
+
 def site_return_levels(scan, site_lon, site_lat, total_years, return_periods=DEFAULT_RETURN_PERIODS, key='site_max',
                        max_bytes=2 ** 31, n_trk=None, engine=None, device=0, tail_exceedances=None):
     """The level of every return period at every site, by a blocked pass over a site analysis.
@@ -163,33 +201,17 @@ def site_return_levels(scan, site_lon, site_lat, total_years, return_periods=DEF
         raise ValueError('give 1 to %d return periods' % _lib.SELECT_MAX_RANKS)
     if tail_exceedances is not None:
         tail_exceedances = _check_tail(tail_exceedances, int(total_years), return_periods)[0]
-    max_bytes = int(max_bytes)
-    if max_bytes < 1:
-        raise ValueError('max_bytes must be >= 1')
-    fl = analysis.Flavour(site_lon)
+    fl, site_lon, site_lat, max_bytes = check_sites(site_lon, site_lat, max_bytes)
     xp = fl.xp
-    site_lon, site_lat = (fl.conv(a).reshape(-1) for a in (site_lon, site_lat))
     n_site = int(site_lon.shape[0])
-    if int(site_lat.shape[0]) != n_site or n_site < 1:
-        raise ValueError('site_lon and site_lat must be non-empty and of one length')
-    if not bool(xp.isfinite(site_lon).all()) or not bool(xp.isfinite(site_lat).all()):
-        raise ValueError('site coordinates must be finite')
-    order = spatial_order(site_lon, site_lat, xp)
-    slon, slat = site_lon[order], site_lat[order]
     level = fl.new((n_site, k.size), 'f8')
     reach = fl.new((n_site,), 'i4')
     tail = None if tail_exceedances is None else (fl.new((n_site, k.size), 'f8'), fl.new((n_site, 3), 'f8'))
-    block_of = lambda n: max(SITE_BLOCK, max_bytes // (8 * max(int(n), 1))) // SITE_BLOCK * SITE_BLOCK        # noqa: E731
-    counts, thr, block = None, None, SITE_BLOCK if n_trk is None else block_of(n_trk)
-    i = 0
-    while i < n_site:
-        j = min(i + block, n_site)
-        res = scan(slon[i:j], slat[i:j])
-        plane = res.pop(key)
+    counts, thr, order = None, None, None
+    for i, j, plane, res, order in site_blocks(scan, fl, site_lon, site_lat, key, max_bytes, n_trk):
         if i == 0:
             thr = res['thresholds']
             counts = fl.new((n_site,) + tuple(res['counts'].shape[1:]), 'i4')
-            block = block_of(plane.shape[1])
         if int(plane.shape[1]) >= 1:
             level[i:j], reach[i:j] = row_select(plane, k, return_valid=True, engine=engine, device=device)
         else:                                               # no storms at all
@@ -203,7 +225,6 @@ def site_return_levels(scan, site_lon, site_lat, total_years, return_periods=DEF
                 tail[0][i:j], tail[1][i:j] = np.nan, np.nan
         counts[i:j] = res['counts']
         del plane, res
-        i = j
 
     def by_site(a):
         out = xp.empty_like(a)

@@ -117,9 +117,11 @@ def parse_args(argv=None):
     p.add_argument('--thresholds', type=lambda t: analysis.parse_range(t, '--thresholds'), default=None, metavar='LO:HI:STEP',
                    help='mm (total) or mm/h (peak-rate); default for total: %s' % ' '.join('%g' % t for t in DEFAULT_RAIN_THRESHOLDS))
     analysis.add_return_period_arg(p, 'storm-total rain (mm) or peak rain rate (mm/h)')
+    analysis.add_events_arg(p, 'storm-total rain (mm) or peak rain rate (mm/h)')
     analysis.add_track_args(p, 'rain.npz')
     a = p.parse_args(argv)
     analysis.check_return_period_args(p, a)
+    analysis.check_events_args(p, a)
     if not (a.site or a.sites or a.grid):
         p.error('give sites with --site, --sites or --grid')
     if a.thresholds is None:
@@ -157,6 +159,10 @@ def main(argv=None):
     analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp, unit=unit)
     if more:
         levels.print_return_levels(res, site_lon, site_lat, unit=unit)
+    if args.events_out is not None:
+        from . import events
+        events.write_cli_events(args, lambda t, x, y: site_rain(t[0], t[1], t[2], groups, x, y, dt, return_values=True, **kw),
+                                (lon, lat, vmax), site_lon, site_lat, STATS[args.stat][1], unit, groups, gfile, gyear)
     return 0
 
 

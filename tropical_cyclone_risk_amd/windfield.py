@@ -132,9 +132,11 @@ def parse_args(argv=None):
     analysis.add_footprint_args(p)
     analysis.add_threshold_arg(p)
     analysis.add_return_period_arg(p, 'peak wind (m/s)')
+    analysis.add_events_arg(p, 'peak wind (m/s)')
     analysis.add_track_args(p, 'wind.npz')
     a = p.parse_args(argv)
     analysis.check_return_period_args(p, a)
+    analysis.check_events_args(p, a)
     if not (a.site or a.sites or a.grid):
         p.error('give sites with --site, --sites or --grid')
     return a
@@ -168,6 +170,10 @@ def main(argv=None):
     analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp)
     if more:
         levels.print_return_levels(res, site_lon, site_lat)
+    if args.events_out is not None:
+        from . import events
+        events.write_cli_events(args, lambda t, x, y: site_wind(t[0], t[1], t[2], t[3], groups, x, y, dt, return_max=True, **kw),
+                                (lon, lat, v, tuple(env)), site_lon, site_lat, 'site_max', 'm/s', groups, gfile, gyear)
     return 0
 
 
