@@ -837,6 +837,49 @@ int tcr_duration_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_win
 /* (site, record) pairs the last tcr_duration_* call of this context evaluated after culling; waits for that call */
 int tcr_duration_pairs(tcr_ctx *ctx, int64_t *pairs);
 
+/* ---- rain accumulation windows: peak D-hour rain depth at sites ------------------------------------------------------- */
+/* replaces: nothing in the reference's code; what lies between the rainfall footprint's two statistics.  The storm total is the
+ * rain of a window longer than the track, the peak rate that of a window of no length; flood and drainage work needs the largest
+ * depth in any 6, 12, 24 or 72 consecutive hours, and its return levels: the depth-duration-frequency table of a site.  The
+ * hourly series of every (site, storm) pair is far too large to store, so the window maximum is formed inside the scan, for up
+ * to 8 window lengths at once.
+ *   track, records, sub-steps, inclusion and the rate of a (site, record) pair: those of the rainfall footprint above, bit for bit
+ *                   (n samples, nr = (n - 1) substeps + 1 records).
+ *   h               dt_s / (3600 substeps) hours.
+ *   rho_q           the rate (mm/h) of record q at the site if the pair is included (r <= r_out_km), else 0.
+ *   I_q             (h / 2) (rho_q + rho_q+1), q = 0 .. nr - 2: the trapezoid of one sub-interval.
+ *   T_k             the sum of I_q over q < k substeps, added in ascending q; T_0 = 0.  The depth up to sample k = 0 .. n - 1.
+ *   windows         n_window lengths m_i in samples (window_samples, int32), 1 <= n_window <= 8, 1 <= m_i <= 96, strictly ascending.
+ *   A_i             max over k = 0 .. n - 1 of T_k - T_max(k - m_i, 0)   (mm).
+ *   site_window     a host array of n_window device pointers (host pointers in tcr_accumulation_host); the array may be NULL, and
+ *                   so may any entry (not written).  Entry i is a [n_site][n_trk] plane of A_i; NaN where no record of the storm
+ *                   is included at the site (so in every window alike).  It can be 0.0.
+ *   counts          [n_site][n_group][n_window][n_bin] (int32): storms s in [group_off[g], group_off[g + 1]) with
+ *                   A_i >= thresholds[b] (mm).  A NaN counts nowhere.
+ * Consequences: windows start and end on track samples (sub-steps refine the integral inside a sample interval, not the window's
+ * position).  A window of m_i >= n - 1 samples gives T_n-1, the storm total by the trapezoid rule of TCR_RAIN_TOTAL, equal to it
+ * up to the rounding of the two summations.  A_i is non-decreasing in m_i exactly, also in floating point (T is a non-decreasing
+ * sequence and subtraction is monotone), and A_i <= m_i (dt_s / 3600) times the peak rate of TCR_RAIN_PEAK_RATE.
+ * Arguments: tracks and prm under exactly the rules of tcr_rainfall_*, and prm->stat == TCR_RAIN_TOTAL; the windows as above;
+ * n_window * (n_bin + 1) <= 64; 512 (m_max + 1) + 256 n_window (n_bin + 1) <= 65536, the LDS bytes of a wave (m_max: the longest
+ * window).  Every message begins with "tcr_accumulation:" and nothing is launched after one.
+ * Not modelled: window positions between samples; rain asymmetry and decay after landfall, as in the rainfall footprint.
+ * T of a (site, storm) is one accumulator over the included records in record order, whatever else the call holds (the terms of
+ * records that are not included are exact zeros, so skipping them changes no bits), a window's value is a difference and a max
+ * of such sums and the counts are integers: every output is bit-identical from run to run, whatever the launch shape, the site
+ * order or the storm order.  _dev: planes, sites, counts and the planes site_window points to are device memory, asynchronous on
+ * `stream`; window_samples, thresholds, group_off and the site_window pointer array are host memory in both entry points.  The
+ * workspace is the context's seventh: calls of tcr_accumulation_* on one context must be ordered, but one may be in flight next
+ * to a call of any other analysis, tcr_rainfall_* included, on another stream. */
+int tcr_accumulation_dev(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const tcr_rain_params *prm, int64_t n_site,
+                         const double *site_lon, const double *site_lat, int32_t n_window, const int32_t *window_samples, int32_t n_bin,
+                         const double *thresholds, int32_t *counts, double *const *site_window, void *stream);
+int tcr_accumulation_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const tcr_rain_params *prm, int64_t n_site,
+                          const double *site_lon, const double *site_lat, int32_t n_window, const int32_t *window_samples, int32_t n_bin,
+                          const double *thresholds, int32_t *counts, double *const *site_window);
+/* (site, record) pairs the last tcr_accumulation_* call of this context evaluated after culling; waits for that call */
+int tcr_accumulation_pairs(tcr_ctx *ctx, int64_t *pairs);
+
 /* ---- row selection (return levels): the k-th largest value of every row of a per-storm plane ----------------------------- */
 /* replaces: nothing in the reference's code; the inverse of the return periods above.  With return_period = total_years /
  * count(peak >= v), the level of period T at a site is the k-th largest storm peak there, k the smallest integer with

@@ -26,7 +26,9 @@ namespace {
 constexpr int kRfMaxSub = 64;
 
 // one sample or sub-sample (128 bytes): half-angle terms of the centre (distance), full-angle terms (the cap's centre), the
-// profile in mm/h and km, and the weight in hours
+// profile in mm/h and km, and the weight in hours; then pad0 and pad1, which k_rain_prep fills with the record's index in its
+// track and whether it is the track's last (int64 in the slots' bits).  uniform() does not load them: only the accumulation
+// windows read them (AcRec, tcr_accumulation.hip)
 struct RfRec {
     double sp, cp, sl, cl, cosp, t0, slope, tm, rm, ire, w, sinp, sinl, cosl, pad0, pad1;
     static __device__ __forceinline__ RfRec uniform(const RfRec *p)
@@ -73,11 +75,17 @@ __device__ __forceinline__ RfRec rf_sub_record(const RfPrepArgs &a, const double
     const int k = q / a.sub, j = q - k * a.sub;
     const double w = (q == 0 || q == nr - 1) ? 0.5 * a.w : a.w;
     const double x = lon[k], y = lat[k], v = vv[k];
-    if (j == 0) return rf_record(a, x, y, v, w);
-    const double tau = (double)j / (double)a.sub;
-    double dl = lon[k + 1] - x;
-    dl -= 360.0 * floor((dl + 180.0) / 360.0);          // [-180, 180)
-    return rf_record(a, x + tau * dl, y + tau * (lat[k + 1] - y), v + tau * (vv[k + 1] - v), w);
+    RfRec r;
+    if (j == 0) r = rf_record(a, x, y, v, w);
+    else {
+        const double tau = (double)j / (double)a.sub;
+        double dl = lon[k + 1] - x;
+        dl -= 360.0 * floor((dl + 180.0) / 360.0);      // [-180, 180)
+        r = rf_record(a, x + tau * dl, y + tau * (lat[k + 1] - y), v + tau * (vv[k + 1] - v), w);
+    }
+    r.pad0 = __longlong_as_double(q);                   // (AcRec, tcr_accumulation.hip)
+    r.pad1 = __longlong_as_double(q == nr - 1 ? 1 : 0);
+    return r;
 }
 
 __global__ __launch_bounds__(64) void k_rain_prep(RfPrepArgs a)

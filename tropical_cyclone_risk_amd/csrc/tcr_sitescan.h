@@ -1,5 +1,5 @@
 // The site scan: what the per-site analyses of a track ensemble share.  Its users: tcr_hazard.hip, tcr_windfield.hip,
-// tcr_loss.hip, tcr_rainfall.hip, tcr_compound.hip, tcr_duration.hip.  Each of them turns every storm into a row of wave-uniform
+// tcr_loss.hip, tcr_rainfall.hip, tcr_compound.hip, tcr_duration.hip, tcr_accumulation.hip.  Each of them turns every storm into a row of wave-uniform
 // records, accumulates something per (site, storm) over the storm's records with haversine(site, record) <= R, and counts the
 // storms of every group by what was accumulated.  In the plainest form (ScanPeak below):
 //

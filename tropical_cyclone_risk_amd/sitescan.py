@@ -1,5 +1,5 @@
 """The Python side of the per-site scan (csrc/tcr_sitescan.h), which site hazard, wind footprint, portfolio loss, rainfall and
-compound hazard and wind duration share: the checks of sites and groups, the order the kernel wants (the storms of a group next to each other, the
+compound hazard, wind duration and rain accumulation windows share: the checks of sites and groups, the order the kernel wants (the storms of a group next to each other, the
 sites in Z-order), the call, and the way back to the caller's site and storm order."""
 import collections
 import ctypes as C
