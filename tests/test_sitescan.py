@@ -1,6 +1,7 @@
-"""The permutation round trip of sitescan.site_scan, for its six users: whatever order the caller's sites and storms are in,
-every returned array is, bit for bit, that of the same call on sites and storms already in the order the front end chooses
-(storms of a group next to each other, sites in Z-order), mapped back to the caller's order."""
+"""The permutation round trip of sitescan.site_scan, for its seven users (eight calls: the rainfall has two statistics).
+Whatever order the caller's sites and storms are in, every returned array is, bit for bit, that of the same call on sites and
+storms already in the order the front end chooses (storms of a group next to each other, sites in Z-order), mapped back to the
+caller's order."""
 import numpy as np
 import pytest
 
@@ -8,13 +9,15 @@ N_T, N_GROUPS, DT = 5, 3, 3600.0
 THR = np.array([20.0, 35.0, 50.0])
 RTHR = {'total': np.array([1.0, 10.0, 30.0]), 'peak-rate': np.array([0.5, 3.0, 8.0])}      # mm, mm/h
 LEVELS, HOURS = np.array([20.0, 35.0]), np.array([1.0, 2.0, 3.0])                           # m/s, hours (a track lasts 4)
+WINDOWS_H = (1.0, 3.0)                  # hours: 1 and 3 samples of DT
 # 49 storms: group sizes 33 / 0 / 16.  A chunk of the scan holds at least 16 storms, so the first group spans three chunks
 # (16 + 16 + 1): the cross-chunk reductions and the per-chunk histograms' sums have more than one term
 N_TRK = (0, 1, 17, 49)
 N_SITE = (1, 64, 65)                    # one lane, a full tile, a second tile with one lane
 # (5 - 1) 8 + 1 = 33 records: two culling segments, the second with one record and padding
 SUBSTEPS = 8
-NAMES = ['site_hazard', 'site_wind', 'portfolio_loss', 'site_rain-total', 'site_rain-peak-rate', 'site_compound', 'site_duration']
+NAMES = ['site_hazard', 'site_wind', 'portfolio_loss', 'site_rain-total', 'site_rain-peak-rate', 'site_compound', 'site_duration',
+         'site_accumulation']
 PAIR_PLANES = ('site_max', 'site_total', 'site_peak_rate', 'site_wind', 'site_rain')        # [n_site][n_trk]
 
 
@@ -44,7 +47,7 @@ def _sites(rng, n):
 
 
 def _run(name, P, groups, slon, slat, value, v_half, substeps=1):
-    from tropical_cyclone_risk_amd import compound, duration, hazard, loss, rainfall, windfield
+    from tropical_cyclone_risk_amd import accumulation, compound, duration, hazard, loss, rainfall, windfield
     if name == 'site_hazard':
         return hazard.site_hazard(P['lon'], P['lat'], P['vmax'], groups, slon, slat, radius_km=300.0, thresholds=THR,
                                   return_max=True, n_groups=N_GROUPS)
@@ -52,6 +55,9 @@ def _run(name, P, groups, slon, slat, value, v_half, substeps=1):
         stat = name[len('site_rain-'):]
         return rainfall.site_rain(P['lon'], P['lat'], P['vmax'], groups, slon, slat, DT, stat=stat, substeps=substeps,
                                   thresholds=RTHR[stat], return_values=True, n_groups=N_GROUPS)
+    if name == 'site_accumulation':
+        return accumulation.site_accumulation(P['lon'], P['lat'], P['vmax'], groups, slon, slat, DT, windows_h=WINDOWS_H,
+                                              thresholds=RTHR['total'], substeps=substeps, return_values=True, n_groups=N_GROUPS)
     env = [P[k] for k in ('u250', 'v250', 'u850', 'v850')]
     if name == 'site_wind':
         return windfield.site_wind(P['lon'], P['lat'], P['v'], env, groups, slon, slat, DT, substeps=substeps, thresholds=THR,
@@ -75,6 +81,8 @@ def _echo(name, substeps):
         return dict(wind_thresholds=THR, rain_thresholds=RTHR['total'])
     if name == 'site_duration':
         return dict(thresholds=HOURS, levels=LEVELS, hours_per_half_step=duration.hours_per_half_step(DT, substeps))
+    if name == 'site_accumulation':
+        return dict(thresholds=RTHR['total'], windows_h=np.array(WINDOWS_H), window_samples=np.array([1, 3], dtype=np.int32))
     return dict(thresholds=THR)
 
 
@@ -120,9 +128,9 @@ def test_gpu_results_come_back_in_the_callers_order(built_lib, name):
                 elif k in PAIR_PLANES:
                     want[k] = np.empty_like(a)
                     want[k][np.ix_(site_order, order)] = a
-                elif k == 'site_hours':                                 # a 'pair' plane per level
+                elif k in ('site_hours', 'site_window'):                # a 'pair' plane per level or window
                     want[k] = np.empty_like(a)
-                    want[k][np.ix_(np.arange(LEVELS.size), site_order, order)] = a
+                    want[k][np.ix_(np.arange(a.shape[0]), site_order, order)] = a
                 elif k == 'event_loss':
                     want[k] = np.empty_like(a)
                     want[k][order] = a
@@ -133,11 +141,14 @@ def test_gpu_results_come_back_in_the_callers_order(built_lib, name):
                           year_max=(N_GROUPS,), site_loss=(n_site,), thresholds=THR.shape, site_total=(n_site, n_trk),
                           site_peak_rate=(n_site, n_trk), site_wind=(n_site, n_trk), site_rain=(n_site, n_trk),
                           wind_thresholds=THR.shape, rain_thresholds=THR.shape, levels=LEVELS.shape, hours_per_half_step=(),
-                          half_steps=(n_site, N_GROUPS, LEVELS.size), site_hours=(LEVELS.size, n_site, n_trk))
+                          half_steps=(n_site, N_GROUPS, LEVELS.size), site_hours=(LEVELS.size, n_site, n_trk),
+                          windows_h=(len(WINDOWS_H),), window_samples=(len(WINDOWS_H),), site_window=(len(WINDOWS_H), n_site, n_trk))
             if name == 'site_compound':
                 shapes['counts'] = (n_site, N_GROUPS, THR.size + 1, THR.size + 1)
             elif name == 'site_duration':
                 shapes['counts'] = (n_site, N_GROUPS, LEVELS.size, HOURS.size)
+            elif name == 'site_accumulation':
+                shapes['counts'] = (n_site, N_GROUPS, len(WINDOWS_H), THR.size)
             for k in want:
                 assert np.shape(got[k]) == shapes[k] and _same_bits(got[k], want[k]), (k, n_site, n_trk, substeps)
 
@@ -167,6 +178,30 @@ def test_gpu_results_come_back_in_the_callers_order(built_lib, name):
                 elif name == 'site_duration':
                     assert (got['half_steps'][:, 0] > 0).sum() > 1 and not got['half_steps'][:, 1].any()
                     assert np.isfinite(got['site_hours']).sum() > n_site and (got['site_hours'] > 0).sum() > n_site
+                elif name == 'site_accumulation':
+                    assert np.isfinite(got['site_window']).sum() > n_site
                 else:
                     plane = [k for k in PAIR_PLANES if k in got]
                     assert len(plane) == 1 and np.isfinite(got[plane[0]]).sum() > n_site
+
+
+@pytest.mark.parametrize('arg_name,row_name', [('return_hours', 'level'), ('return_values', 'window')])
+def test_wanted_rows(arg_name, row_name):
+    """The rows whose planes a stacked analysis returns: duration's return_hours and accumulation's return_values."""
+    from tropical_cyclone_risk_amd.sitescan import wanted_rows
+    rows = lambda v, n=4: wanted_rows(v, n, arg_name, row_name)                             # noqa: E731
+    assert rows(True) == [0, 1, 2, 3] and rows(True, 1) == [0]
+    assert rows(False) == [] and rows(None) == [] and rows([]) == [] and rows(()) == []
+    assert rows([2, 0]) == [0, 2] and rows((3, 1, 2)) == [1, 2, 3] and rows([1.0]) == [1]
+    got = rows(np.array([3, 0], dtype=np.int64))
+    assert got == [0, 3] and all(type(i) is int for i in got)
+    not_a_list = '%s must be True, False or a list of distinct %s indices' % (arg_name, row_name)
+    for bad in ([1, 1], (0, 2, 0), np.array([2, 2]), [True], [0, False], [0.5], [1, 'a'], ['1'], 3, 'all', [None], [[0]]):
+        with pytest.raises(ValueError) as e:
+            rows(bad)
+        assert str(e.value) == not_a_list, bad
+    for bad in ([4], [-1], (0, 7), np.array([1, 4])):
+        with pytest.raises(ValueError) as e:
+            rows(bad)
+        assert str(e.value) == '%s names a %s that does not exist' % (arg_name, row_name), bad
+    assert rows([3]) == [3] and rows([0], 1) == [0]

@@ -32,7 +32,7 @@ import numpy as np
 
 from . import _lib, analysis, hazard, rainfall
 from .rainfall import DEFAULT_RAIN_THRESHOLDS
-from .sitescan import site_scan
+from . import sitescan
 
 MAX_WINDOWS = 8
 MAX_WINDOW_SAMPLES = 96
@@ -60,11 +60,8 @@ def site_accumulation(lon, lat, vmax, groups, site_lon, site_lat, dt_s, windows_
                     v_hi_kt, want, engine, device, n_groups)
     planes = res.pop('planes')
     if return_values is not False and return_values is not None:
-        n_site, n_trk = int(res['counts'].shape[0]), int(lon.shape[0]) if hasattr(lon, 'shape') else len(lon)
-        out = fl.new((m.size, n_site, n_trk), 'f8')
-        for i in range(m.size):
-            out[i] = planes[i] if i in planes else np.nan
-        res['site_window'] = out
+        n_trk = int(lon.shape[0]) if hasattr(lon, 'shape') else len(lon)
+        res['site_window'] = sitescan.stacked_planes(fl, planes, m.size, int(res['counts'].shape[0]), n_trk)
     return res
 
 
@@ -96,20 +93,7 @@ def _check_windows(windows_h, dt_s, thresholds, return_values):
         raise ValueError('n_window * (n_bin + 1) must be <= %d' % MAX_CELLS)
     if 512 * (int(m[-1]) + 1) + 256 * m.size * (thr.size + 1) > MAX_LDS:
         raise ValueError('512 (longest window in samples + 1) + 256 n_window (n_bin + 1) must be <= %d' % MAX_LDS)
-    if return_values is True:
-        want = list(range(m.size))
-    elif return_values is False or return_values is None:
-        want = []
-    else:
-        try:
-            want = sorted({int(i) for i in return_values if int(i) == i and not isinstance(i, bool)})
-            if len(want) != len(list(return_values)):
-                raise ValueError
-        except (TypeError, ValueError):
-            raise ValueError('return_values must be True, False or a list of distinct window indices')
-        if any(not 0 <= i < m.size for i in want):
-            raise ValueError('return_values names a window that does not exist')
-    return win_h, m, want
+    return win_h, m, sitescan.wanted_rows(return_values, m.size, 'return_values', 'window')
 
 
 def _scan(lon, lat, vmax, groups, site_lon, site_lat, dt_s, win_h, m, thresholds, r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt,
@@ -118,22 +102,15 @@ def _scan(lon, lat, vmax, groups, site_lon, site_lat, dt_s, win_h, m, thresholds
     Flavour)."""
     planes, fl, thr, prm, _ = rainfall._prepare(lon, lat, vmax, dt_s, 'total', r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt,
                                                 thresholds, n_groups)
-    n_window, n_bin = int(m.size), int(thr.size)
-    outputs = [('window%d' % i, 'pair') for i in want]
+    n_window = int(m.size)
 
-    def make_args(a):
+    def make_args(a, win):
         lon_, lat_, vmax_ = a.planes
         n_bin_, thr_, counts_, _ = a.out
-        win = (C.c_void_p * n_window)()
-        for i, p in zip(want, a.outputs):
-            win[i] = p
         return (C.byref(_lib.HazardTracks(lon=lon_, lat=lat_, vmax=vmax_, **a.tracks)), C.byref(prm)) + a.sites + \
-            (n_window, m.ctypes.data_as(C.POINTER(C.c_int32)), n_bin_, thr_, counts_, win if want else None)
-    res = site_scan('tcr_accumulation', planes, fl, groups, n_groups, site_lon, site_lat, thr, False, engine, device, make_args,
-                    more_outputs=outputs, count_cells=n_window * n_bin)
-    n_site, n_grp = int(res['counts'].shape[0]), int(res['counts'].shape[1])
-    res['counts'] = res['counts'].reshape(n_site, n_grp, n_window, n_bin)
-    res['planes'] = {i: res.pop('window%d' % i) for i in want}
+            (n_window, m.ctypes.data_as(C.POINTER(C.c_int32)), n_bin_, thr_, counts_, win)
+    res = sitescan.stacked_scan('tcr_accumulation', planes, fl, groups, n_groups, site_lon, site_lat, thr, n_window, want, 'window',
+                                engine, device, make_args)
     res['windows_h'] = win_h
     res['window_samples'] = m
     return res, fl
@@ -189,18 +166,13 @@ def main(argv=None):
                             device=args.device, **kw)
     more = {}
     if args.return_periods is not None:
-        from . import levels as rl
-        per_window = []
-        for i in range(m.size):                             # one blocked pass per window, with that window's plane only
-            def one(t, x, y, i=i):
-                r, _ = _scan(t[0], t[1], t[2], groups, x, y, dt, win_h, m, args.thresholds, kw['r_out_km'], kw['substeps'], None, 35., 155.,
-                             [i], None, 0, total_years)
-                r['depth'] = r.pop('planes')[i]
-                return r
-            per_window.append(rl.device_levels(one, (lon, lat, vmax), site_lon, site_lat, total_years, args.return_periods, 'depth',
-                                               args.device))
-        more = dict(return_level=np.stack([r['return_level'] for r in per_window], axis=1), return_periods=per_window[0]['return_periods'],
-                    n_reach=per_window[0]['n_reach'])
+        def one(i, t, x, y):
+            r, _ = _scan(t[0], t[1], t[2], groups, x, y, dt, win_h, m, args.thresholds, kw['r_out_km'], kw['substeps'], None, 35., 155.,
+                         [i], None, 0, total_years)
+            r['value'] = r.pop('planes')[i]
+            return r
+        more = sitescan.stacked_return_levels(one, m.size, (lon, lat, vmax), site_lon, site_lat, total_years, args.return_periods,
+                                              args.device)
     rp = hazard.return_periods(res['counts'], total_years)
     np.savez(args.out, counts=res['counts'], return_period=rp, windows_h=win_h, window_samples=m, thresholds=res['thresholds'],
              site_lon=site_lon, site_lat=site_lat, total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps, dt_s=dt,

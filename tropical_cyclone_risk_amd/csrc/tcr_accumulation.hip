@@ -11,16 +11,17 @@
 //
 // A user of the site scan (tcr_sitescan.h: tiling, culling, the mode protocol) on the rainfall footprint's records: the prep
 // kernel is k_rain_prep itself, the rate of a pair is RainScan<false>'s.  What is the accumulation's own:
-//   AcRec             RfRec read with the two slots RfRec::uniform leaves alone: the record's index in its track, and whether it
-//                     is the track's last;
-//   AccumScan<NW>     the policy of k_site_scan: the rate, the half step h / 2, the windows and where the planes go;
-//   ScanWindows<NW>   the mode (1 <= NW <= kScanMaxWindow): the first whose state of a storm is a time series.  Per lane and storm
+//   AccumScan<NW>     the policy of k_site_scan: the rate, the half step h / 2, the windows and where the planes go.  The record's
+//                     index in its track and whether it is the track's last are RfRec's q and end;
+//   ScanWindows<NW>   the mode (1 <= NW <= kScanMaxRow): the first whose state of a storm is a time series.  Per lane and storm
 //                     in registers: the index and rate of the last included record, the running T up to that record, the number of
 //                     sample boundaries passed, the first boundary this storm wrote, the ring position and best[NW] (fixed arrays,
 //                     fully unrolled, never indexed by a run-time value).  Per lane in the wave's LDS, behind the histogram
 //                     cells: a ring of m_max + 1 values of T at the last sample boundaries, [slot][lane] in doubles, so that a
 //                     lane stays in its own pair of banks whatever slot it is at (the lanes' catch-up loops are at different
-//                     slots).
+//                     slots).  Per storm each of the call's n_row windows has the value best[i] (NaN when no record was
+//                     included): a row of the stacked histogram (ScanStack, tcr_sitescan.h: the plane, the rank, the partial
+//                     counts).
 //
 // k_site_scan calls add only for included pairs and skips culled segments for the whole wave, so the mode catches up inside add
 // and end_storm.  The records between the last included one and this one had rate 0: T first takes (h / 2) rho_last, is constant
@@ -41,33 +42,13 @@
 
 namespace {
 
-constexpr int kScanMaxWindow = 8;           // window accumulators of a ScanWindows mode
-constexpr int kAcMaxWindow = kScanMaxWindow;
 constexpr int kAcMaxSamples = 96;           // the longest window, in samples
 constexpr size_t kAcMaxLds = 65536;         // of a wave: what a launch may ask for without an attribute
 
-// a rainfall record as the accumulation scan reads it: the terms RfRec::uniform loads, and the two slots as the integers
-// k_rain_prep stored
-struct AcRec {
-    double sp, cp, sl, cl, cosp, t0, slope, tm, rm, ire, w, sinp, sinl, cosl;
-    int64_t q, end;
-    static __device__ __forceinline__ AcRec uniform(const AcRec *p)
-    {
-        const double *d = &p->sp;
-        return AcRec{hz_uniform(d), hz_uniform(d + 1), hz_uniform(d + 2), hz_uniform(d + 3), hz_uniform(d + 4), hz_uniform(d + 5),
-                     hz_uniform(d + 6), hz_uniform(d + 7), hz_uniform(d + 8), hz_uniform(d + 9), 0.0, 0.0, 0.0, 0.0,
-                     hz_uniform(&p->q), hz_uniform(&p->end)};
-    }
-    __device__ __forceinline__ RfRec rain() const { return RfRec{sp, cp, sl, cl, cosp, t0, slope, tm, rm, ire, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; }
-};
-static_assert(sizeof(AcRec) == sizeof(RfRec) && offsetof(AcRec, q) == offsetof(RfRec, pad0) && offsetof(AcRec, end) == offsetof(RfRec, pad1) &&
-              offsetof(AcRec, ire) == offsetof(RfRec, ire), "AcRec is RfRec's layout");
-
-// the mode of AccumScan (header comment); cells [n_window][n_hbin + 1][64] of int32: the storms of this lane whose depth in the
-// window passes exactly k thresholds; then the ring, [n_slot][64] of double
+// the mode of AccumScan (header comment), on ScanStack with the windows for rows; in the wave's LDS behind the histogram's cells
+// the ring, [n_slot][64] of double
 template <int NW>
 struct ScanWindows {
-    static_assert(NW >= 1 && NW <= kScanMaxWindow, "a window mode has 1 to kScanMaxWindow window accumulators");
     struct Storm {
         int32_t last = -1;                  // the last included record (-1: none yet),
         int32_t end = 0;                    // whether it is the track's last,
@@ -82,14 +63,12 @@ struct ScanWindows {
     int32_t n_slot;                         // m_max + 1
     static ScanShape shape(int32_t n_window, int32_t n_hbin, int32_t m_max, const double *thr)
     {
-        return ScanShape{n_window * n_hbin, sizeof(int32_t) * 64 * (size_t)n_window * (n_hbin + 1) + sizeof(double) * 64 * ((size_t)m_max + 1),
-                         n_hbin, thr};
+        return ScanStack::shape(n_window, n_hbin, sizeof(double) * 64 * ((size_t)m_max + 1), thr);
     }
     template <class P> __device__ __forceinline__ void begin(const P &pol, const ScanLane &c)
     {
-        const int n = pol.n_window * (pol.n_hbin + 1);
-        for (int k = 0; k < n; ++k) c.lds[k * 64 + c.lane] = 0;
-        ring = reinterpret_cast<double *>(c.lds + n * 64) + c.lane;
+        ScanStack::begin(c, pol.out.n_row, pol.out.n_hbin);
+        ring = reinterpret_cast<double *>(c.lds + pol.out.n_row * (pol.out.n_hbin + 1) * 64) + c.lane;
         n_slot = pol.n_slot;
     }
     // boundary st.nb, which has (or would have) the ring position st.slot, has the depth T: every window's T - T_(nb - m), where
@@ -98,7 +77,7 @@ struct ScanWindows {
     {
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
-            if (i < pol.n_window) {                     // (wave-uniform)
+            if (i < pol.out.n_row) {                    // (wave-uniform)
                 int s = st.slot - pol.m[i];
                 if (s < 0) s += n_slot;                 // (m <= m_max = n_slot - 1: 0 <= s < n_slot)
                 const double prev = st.nb - pol.m[i] < st.k0 ? 0.0 : ring[s * 64];
@@ -139,48 +118,31 @@ struct ScanWindows {
         if (on) emit(pol, st, st.T);
         st.last = iq; st.rho = rho; st.end = (int32_t)p.end;
     }
-    // the trailing half interval, a plane and a rank per window; a storm without an included record counts nowhere
+    // the trailing half interval, and a row per window; a storm without an included record counts nowhere
     template <class P> __device__ __forceinline__ void end_storm(const P &pol, const ScanLane &c, const Storm &st0, int64_t s, bool)
     {
         Storm st = st0;
         const bool any = st.last >= 0;
         if (any && !st.end) eval(pol, st, st.T + pol.hh * st.rho);
 #pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            if (i < pol.n_window) {                     // (wave-uniform)
-                const double d = any ? st.best[i] : NAN;
-                if (pol.site_window[i] && c.valid) pol.site_window[i][c.site * c.a.n_trk + s] = d;
-                if (any) c.lds[(i * (pol.n_hbin + 1) + scan_rank(c.a.thr, pol.n_hbin, d)) * 64 + c.lane] += 1;
-            }
-        }
+        for (int i = 0; i < NW; ++i)
+            if (i < pol.out.n_row) ScanStack::finish(pol.out, c, i, s, any, any ? st.best[i] : NAN);        // (wave-uniform)
     }
-    // at least b + 1 thresholds, per window
-    template <class P> __device__ __forceinline__ void end_chunk(const P &pol, const ScanLane &c)
-    {
-        if (!c.valid) return;
-        int32_t *out = c.a.part + (c.chunk * c.a.n_site + c.site) * c.a.n_cell;
-        for (int i = 0; i < pol.n_window; ++i) {
-            int32_t cl = 0;
-            for (int b = pol.n_hbin - 1; b >= 0; --b) { cl += c.lds[(i * (pol.n_hbin + 1) + b + 1) * 64 + c.lane]; out[i * pol.n_hbin + b] = cl; }
-        }
-    }
+    template <class P> __device__ __forceinline__ void end_chunk(const P &pol, const ScanLane &c) { ScanStack::end_chunk(c, pol.out.n_row, pol.out.n_hbin); }
 };
 
 // the policy of k_site_scan<AccumScan<NW>>: NW accumulators (the call's n_window <= NW)
 template <int NW>
 struct AccumScan {
-    using Rec = AcRec;
+    using Rec = RfRec;
     using Mode = ScanWindows<NW>;
     static constexpr int kUnroll = 2;       // (1 and 4 measured within 3 % of it: profiles/accumulation_unroll_ab.txt)
     RainScan<false> rain;
     double hh;                              // h / 2: hours per half sub-step
-    int32_t substeps, n_window, n_hbin, n_slot;
+    int32_t substeps, n_slot;
     int32_t m[NW];                          // window lengths in samples, ascending; 0 past n_window (T_k - T_k: never wins)
-    double *site_window[NW];                // [n_site][n_trk], or NULL
-    __device__ __forceinline__ double value(const ScanSite &s, const AcRec &p, double q) const
-    {
-        return rain.at_angle(s, p.rain(), scan_pair_angle(q));
-    }
+    ScanStackOut<NW> out;                   // n_window rows; the planes are site_window[i]
+    __device__ __forceinline__ double value(const ScanSite &s, const RfRec &p, double q) const { return rain.value(s, p, q); }
 };
 
 int accumulation_check(tcr_ctx *ctx, const tcr_hazard_tracks *t, const tcr_rain_params *p, int64_t n_site, const double *site_lon,
@@ -190,12 +152,11 @@ int accumulation_check(tcr_ctx *ctx, const tcr_hazard_tracks *t, const tcr_rain_
     if (!window_samples) return fail(ctx, "tcr_accumulation: NULL argument");
     if (rainfall_check(ctx, t, p, n_site, site_lon, site_lat, n_bin, thr, counts, "tcr_accumulation")) return -1;
     if (p->stat != TCR_RAIN_TOTAL) return fail(ctx, "tcr_accumulation: stat must be TCR_RAIN_TOTAL (0)");
-    if (n_window < 1 || n_window > kAcMaxWindow) return fail(ctx, "tcr_accumulation: n_window must be in [1, 8]");
+    if (scan_stack_check(ctx, "tcr_accumulation", "window", n_window, n_bin)) return -1;
     for (int i = 0; i < n_window; ++i)
         if (window_samples[i] < 1 || window_samples[i] > kAcMaxSamples || (i > 0 && window_samples[i] <= window_samples[i - 1]))
             return fail(ctx, "tcr_accumulation: window_samples must be in [1, 96] and strictly ascending");
-    if ((int64_t)n_window * ((int64_t)n_bin + 1) > kHzMaxBin) return fail(ctx, "tcr_accumulation: n_window * (n_bin + 1) must be <= 64");
-    if (ScanWindows<kAcMaxWindow>::shape(n_window, n_bin, window_samples[n_window - 1], thr).lds > kAcMaxLds)
+    if (ScanWindows<kScanMaxRow>::shape(n_window, n_bin, window_samples[n_window - 1], thr).lds > kAcMaxLds)
         return fail(ctx, "tcr_accumulation: 512 (longest window + 1) + 256 n_window (n_bin + 1) must be <= 65536 (the LDS of a wave)");
     return 0;
 }
@@ -213,13 +174,13 @@ hipError_t accumulation_launch(const AcCall &d, const ScanRows<RfRec> &rows, con
 {
     AccumScan<NW> pol{};
     pol.hh = 0.5 * (d.prm->dt_s / (3600.0 * d.prm->substeps));
-    pol.substeps = d.prm->substeps; pol.n_window = d.n_window; pol.n_hbin = d.n_bin;
+    pol.substeps = d.prm->substeps; pol.out.n_row = d.n_window; pol.out.n_hbin = d.n_bin;
     pol.n_slot = d.m[d.n_window - 1] + 1;
     for (int i = 0; i < NW; ++i) {
         pol.m[i] = i < d.n_window ? d.m[i] : 0;
-        pol.site_window[i] = (d.site_window && i < d.n_window) ? d.site_window[i] : nullptr;
+        pol.out.plane[i] = (d.site_window && i < d.n_window) ? d.site_window[i] : nullptr;
     }
-    return scan_launch(k_rain_prep, rain_prep_args(d.t, d.prm, rows), rows.as<AcRec>(), L, pol);     // (the scan sees the rainfall's rows as AcRec)
+    return scan_launch(k_rain_prep, rain_prep_args(d.t, d.prm, rows), rows, L, pol);
 }
 
 }  // namespace
@@ -236,10 +197,10 @@ int tcr_accumulation_dev(tcr_ctx *ctx, const tcr_hazard_tracks *t, const tcr_rai
     const AcCall d{t, prm, n_window, n_bin, window_samples, site_window};
     // (the modes of every NW have the one shape)
     return scan_run<RfRec>(ctx, ctx->an.ac, "tcr_accumulation", t, scan_plan(t, n_site, kScanAnyChunk),
-                           ScanWindows<kAcMaxWindow>::shape(n_window, n_bin, window_samples[n_window - 1], thresholds), n_rec, 0, n_site,
+                           ScanWindows<kScanMaxRow>::shape(n_window, n_bin, window_samples[n_window - 1], thresholds), n_rec, 0, n_site,
                            site_lon, site_lat, prm->r_out_km, kWfEarthR / 1000.0, counts, nullptr, st,
                            [&](const ScanRows<RfRec> &rows, const ScanLaunch &L, void *) {
-        return n_window <= 4 ? accumulation_launch<4>(d, rows, L) : accumulation_launch<kAcMaxWindow>(d, rows, L);
+        return n_window <= 4 ? accumulation_launch<4>(d, rows, L) : accumulation_launch<kScanMaxRow>(d, rows, L);
     });
 }
 
@@ -252,18 +213,13 @@ int tcr_accumulation_host(tcr_ctx *ctx, const tcr_hazard_tracks *t, const tcr_ra
     DevBuf B;
     tcr_hazard_tracks d;
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, n_window * n_bin, false);
-    const size_t n_plane = (size_t)n_site * std::max<int64_t>(1, t->n_trk);
-    double *d_win[kAcMaxWindow] = {};
-    bool ok = hazard_tracks_upload(B, t, &d) && io.ok;
-    for (int i = 0; i < n_window && ok; ++i)
-        if (site_window && site_window[i]) ok = (d_win[i] = B.get<double>(n_plane)) != nullptr;
-    if (!ok) return fail(ctx, "tcr_accumulation_host: device allocation / upload failed");
+    double *d_win[kScanMaxRow] = {};
+    if (!hazard_tracks_upload(B, t, &d) || !io.ok || !scan_host_planes(B, io, n_window, site_window, d_win))
+        return fail(ctx, "tcr_accumulation_host: device allocation / upload failed");
     if (tcr_accumulation_dev(ctx, &d, prm, n_site, io.site_lon, io.site_lat, n_window, window_samples, n_bin, thresholds, io.counts, d_win,
                              ctx->stream))
         return -1;
-    for (int i = 0; i < n_window; ++i)
-        if (d_win[i] && io.n_max)
-            HIPCHK(ctx, hipMemcpyAsync(site_window[i], d_win[i], sizeof(double) * io.n_max, hipMemcpyDeviceToHost, ctx->stream));
+    if (scan_download_planes(ctx, io, n_window, site_window, d_win)) return -1;
     return scan_download(ctx, io, counts, nullptr);
 }
 

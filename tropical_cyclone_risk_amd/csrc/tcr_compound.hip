@@ -58,8 +58,8 @@ struct CpRec {
         return CpRec{a.sp, a.cp, a.sl, a.cl, a.cosp, a.sinp, a.sinl, a.cosl, a.rm, a.mm, a.f2, a.a2, a.be, a.bn,
                      b.t0, b.slope, b.tm, b.rm, b.ire, b.w};
     }
-    __device__ __forceinline__ WfRec wind() const { return WfRec{sp, cp, sl, cl, cosp, sinp, sinl, cosl, wrm, mm, f2, a2, be, bn, 0.0, 0.0}; }
-    __device__ __forceinline__ RfRec rain() const { return RfRec{sp, cp, sl, cl, cosp, t0, slope, tm, rrm, ire, w, sinp, sinl, cosl, 0.0, 0.0}; }
+    __device__ __forceinline__ WfRec wind() const { return WfRec{sp, cp, sl, cl, cosp, sinp, sinl, cosl, wrm, mm, f2, a2, be, bn, 0, 0.0}; }
+    __device__ __forceinline__ RfRec rain() const { return RfRec{sp, cp, sl, cl, cosp, t0, slope, tm, rrm, ire, w, sinp, sinl, cosl, 0, 0}; }
     __device__ void centre(HzCap *out) const { out->x = cosp * cosl; out->y = cosp * sinl; out->z = sinp; }
 };
 
@@ -236,13 +236,13 @@ int tcr_compound_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const double *vmax
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, (n_wbin + 1) * (n_rbin + 1), site_wind != nullptr);
     const size_t n_plane = (size_t)std::max<int64_t>(1, t->n_trk * t->row_stride);
     const double *d_vmax = t->n_trk > 0 ? B.put(vmax, n_plane) : B.get<double>(1);
-    double *d_rain = site_rain ? B.get<double>((size_t)n_site * std::max<int64_t>(1, t->n_trk)) : nullptr;
-    if (!wind_tracks_upload(B, t, &d) || !io.ok || !d_vmax || (site_rain && !d_rain))
+    double *d_rain = nullptr;
+    if (!scan_host_planes(B, io, 1, &site_rain, &d_rain) || !wind_tracks_upload(B, t, &d) || !io.ok || !d_vmax)
         return fail(ctx, "tcr_compound_host: device allocation / upload failed");
     if (tcr_compound_dev(ctx, &d, d_vmax, wp, rp, n_site, io.site_lon, io.site_lat, n_wbin, wthr, n_rbin, rthr, io.counts, io.site_max,
                          d_rain, ctx->stream))
         return -1;
-    if (site_rain && io.n_max) HIPCHK(ctx, hipMemcpyAsync(site_rain, d_rain, sizeof(double) * io.n_max, hipMemcpyDeviceToHost, ctx->stream));
+    if (scan_download_planes(ctx, io, 1, &site_rain, &d_rain)) return -1;
     return scan_download(ctx, io, counts, site_wind);
 }
 

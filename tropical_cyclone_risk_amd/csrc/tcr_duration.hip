@@ -10,19 +10,17 @@
 //
 // A user of the site scan (tcr_sitescan.h: tiling, culling, the mode protocol) on the wind footprint's records: the prep kernel is
 // k_wind_prep itself, the wind of a pair is WindScan's.  What is the duration's own:
-//   DuRec             WfRec read with its half-weight: the one record slot WfRec::uniform leaves alone;
-//   DurationScan      the policy of k_site_scan: WindScan's value, the record's half-weight, the levels and where the planes go;
-//   ScanLevels<NL>    the mode (1 <= NL <= kScanMaxLevel): time instead of a peak.  value(site, record, a) is formed once per
+//   DurationScan      the policy of k_site_scan: WindScan's value, the record's half-weight (WfRec::hw), the levels and where the
+//                     planes go;
+//   ScanLevels<NL>    the mode (1 <= NL <= kScanMaxRow): time instead of a peak.  value(site, record, a) is formed once per
 //                     included pair and compared with the policy's NL ascending level[] (unused ones +inf), and the record's
 //                     integer weight(record) is added to the int32 accumulator of every level the value reaches (>=) and to one
 //                     more that counts the included records.  The NL + 1 accumulators are registers: fixed arrays, fully unrolled,
-//                     never indexed by a run-time value.  Per storm each of the policy's n_level levels has the value
-//                     (double)sum * unit (NaN when no record was included), which the lane that accumulated it writes to the
-//                     policy's site_level[l] (when not NULL) and ranks against the n_hbin thresholds in thr into the level's own
-//                     (n_hbin + 1) cells of the histogram.  The partial counts are [level][threshold]: n_cell = n_level n_hbin,
-//                     which k_hazard_reduce sums unchanged.  Every lane also keeps an int64 total of its sums per level over the
-//                     chunk's storms and writes it to the policy's level_part [n_chunk][n_site][n_level].  There is no max: the
-//                     call's site_max is NULL and nothing reads it;
+//                     never indexed by a run-time value.  Per storm each of the call's n_row levels has the value
+//                     (double)sum * unit (NaN when no record was included): a row of the stacked histogram (ScanStack,
+//                     tcr_sitescan.h: the plane, the rank, the partial counts).  Every lane also keeps an int64 total of its sums
+//                     per level over the chunk's storms and writes it to the policy's level_part [n_chunk][n_site][n_level].
+//                     There is no max: the call's site_max is NULL and nothing reads it;
 //   k_duration_reduce sums the int64 per-chunk totals of each group.
 // No formula is restated here.
 //
@@ -34,44 +32,15 @@
 
 namespace {
 
-constexpr int kScanMaxLevel = 8;            // level accumulators of a ScanLevels mode
-constexpr int kDuMaxLevel = kScanMaxLevel;
-
-// a footprint record as the duration scan reads it: the terms WfRec::uniform loads, and hw as the integer k_wind_prep stored
-struct DuRec {
-    double sp, cp, sl, cl, cosp, sinp, sinl, cosl, rm, mm, f2, a2, be, bn;
-    int64_t hw;
-    double pad1;
-    static __device__ __forceinline__ DuRec uniform(const DuRec *p)
-    {
-        const double *d = &p->sp;
-        return DuRec{hz_uniform(d), hz_uniform(d + 1), hz_uniform(d + 2), hz_uniform(d + 3), hz_uniform(d + 4), hz_uniform(d + 5),
-                     hz_uniform(d + 6), hz_uniform(d + 7), hz_uniform(d + 8), hz_uniform(d + 9), hz_uniform(d + 10), hz_uniform(d + 11),
-                     hz_uniform(d + 12), hz_uniform(d + 13), hz_uniform(&p->hw), 0.0};
-    }
-    __device__ __forceinline__ WfRec wind() const { return WfRec{sp, cp, sl, cl, cosp, sinp, sinl, cosl, rm, mm, f2, a2, be, bn, 0.0, 0.0}; }
-};
-static_assert(sizeof(DuRec) == sizeof(WfRec) && offsetof(DuRec, hw) == offsetof(WfRec, hw) && offsetof(DuRec, bn) == offsetof(WfRec, bn),
-              "DuRec is WfRec's layout");
-
-// the mode of DurationScan (header comment); cells [n_level][n_hbin + 1][64] of int32: the storms of this lane whose hours at the
-// level pass exactly k thresholds
+// the mode of DurationScan (header comment), on ScanStack with the levels for rows
 template <int NL>
 struct ScanLevels {
-    static_assert(NL >= 1 && NL <= kScanMaxLevel, "a level mode has 1 to kScanMaxLevel level accumulators");
     struct Storm {
         int32_t lv[NL] = {};                // the weights of the records that reach each level,
         int32_t lv_in = 0;                  // and of every included record
     };
     int64_t lv_total[NL] = {};              // this site's sums of the chunk's storms, per level
-    static ScanShape shape(int32_t n_level, int32_t n_hbin, const double *thr)
-    {
-        return ScanShape{n_level * n_hbin, sizeof(int32_t) * 64 * (size_t)n_level * (n_hbin + 1), n_hbin, thr};
-    }
-    template <class P> __device__ __forceinline__ void begin(const P &pol, const ScanLane &c)
-    {
-        for (int k = 0; k < pol.n_level * (pol.n_hbin + 1); ++k) c.lds[k * 64 + c.lane] = 0;
-    }
+    template <class P> __device__ __forceinline__ void begin(const P &pol, const ScanLane &c) { ScanStack::begin(c, pol.out.n_row, pol.out.n_hbin); }
     template <class P, class Rec> __device__ __forceinline__ void add(const P &pol, Storm &st, const ScanSite &me, const Rec &p, double q)
     {
         const double v = pol.value(me, p, q);
@@ -80,48 +49,41 @@ struct ScanLevels {
 #pragma unroll
         for (int l = 0; l < NL; ++l) st.lv[l] += v >= pol.level[l] ? h : 0;               // (a NaN reaches none)
     }
-    // a plane and a rank per level; a storm without an included record counts nowhere
+    // a row per level; a storm without an included record counts nowhere
     template <class P> __device__ __forceinline__ void end_storm(const P &pol, const ScanLane &c, const Storm &st, int64_t s, bool)
     {
 #pragma unroll
         for (int l = 0; l < NL; ++l) {
-            if (l < pol.n_level) {                      // (wave-uniform)
-                const double d = st.lv_in ? (double)st.lv[l] * pol.unit : NAN;
-                if (pol.site_level[l] && c.valid) pol.site_level[l][c.site * c.a.n_trk + s] = d;
-                if (st.lv_in) c.lds[(l * (pol.n_hbin + 1) + scan_rank(c.a.thr, pol.n_hbin, d)) * 64 + c.lane] += 1;
+            if (l < pol.out.n_row) {                    // (wave-uniform)
+                ScanStack::finish(pol.out, c, l, s, st.lv_in != 0, st.lv_in ? (double)st.lv[l] * pol.unit : NAN);
                 lv_total[l] += st.lv[l];
             }
         }
     }
-    // at least b + 1 thresholds, per level; and the level's total
+    // the rows' partial counts; and the level's total
     template <class P> __device__ __forceinline__ void end_chunk(const P &pol, const ScanLane &c)
     {
+        ScanStack::end_chunk(c, pol.out.n_row, pol.out.n_hbin);
         if (!c.valid) return;
-        int32_t *out = c.a.part + (c.chunk * c.a.n_site + c.site) * c.a.n_cell;
-        for (int l = 0; l < pol.n_level; ++l) {
-            int32_t cl = 0;
-            for (int b = pol.n_hbin - 1; b >= 0; --b) { cl += c.lds[(l * (pol.n_hbin + 1) + b + 1) * 64 + c.lane]; out[l * pol.n_hbin + b] = cl; }
-        }
 #pragma unroll
         for (int l = 0; l < NL; ++l)
-            if (l < pol.n_level) pol.level_part[(c.chunk * c.a.n_site + c.site) * pol.n_level + l] = lv_total[l];
+            if (l < pol.out.n_row) pol.level_part[(c.chunk * c.a.n_site + c.site) * pol.out.n_row + l] = lv_total[l];
     }
 };
 
 // the policy of k_site_scan<DurationScan<UNIT_C, NL>>: NL accumulators (the call's n_level <= NL)
 template <bool UNIT_C, int NL>
 struct DurationScan {
-    using Rec = DuRec;
+    using Rec = WfRec;
     using Mode = ScanLevels<NL>;
     static constexpr int kUnroll = 2;
     WindScan<UNIT_C> wind;
     double level[NL];                       // ascending; +inf past n_level
     double unit;                            // u: hours per half-weight
-    int32_t n_level, n_hbin;
-    double *site_level[NL];                 // site_hours[l] [n_site][n_trk], or NULL
+    ScanStackOut<NL> out;                   // n_level rows; the planes are site_hours[l]
     int64_t *level_part;                    // [n_chunk][n_site][n_level]
-    __device__ __forceinline__ double value(const ScanSite &s, const DuRec &p, double q) const { return wind.value(s, p.wind(), q); }
-    __device__ __forceinline__ int32_t weight(const DuRec &p) const { return (int32_t)p.hw; }
+    __device__ __forceinline__ double value(const ScanSite &s, const WfRec &p, double q) const { return wind.value(s, p, q); }
+    __device__ __forceinline__ int32_t weight(const WfRec &p) const { return (int32_t)p.hw; }
 };
 
 // half_steps[site][g][l] = sum of the totals of the chunks of group g
@@ -142,11 +104,10 @@ int duration_check(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_params
     if (!levels) return fail(ctx, "tcr_duration: NULL argument");
     if (windfield_check(ctx, t, p, n_site, site_lon, site_lat, n_bin, thr, counts, "tcr_duration")) return -1;
     if (!(thr[0] > 0.0)) return fail(ctx, "tcr_duration: thresholds must be > 0");
-    if (n_level < 1 || n_level > kDuMaxLevel) return fail(ctx, "tcr_duration: n_level must be in [1, 8]");
+    if (scan_stack_check(ctx, "tcr_duration", "level", n_level, n_bin)) return -1;
     for (int l = 0; l < n_level; ++l)
         if (!std::isfinite(levels[l]) || !(levels[l] > 0.0) || (l > 0 && !(levels[l] > levels[l - 1])))
             return fail(ctx, "tcr_duration: levels must be finite, > 0 and ascending");
-    if ((int64_t)n_level * ((int64_t)n_bin + 1) > kHzMaxBin) return fail(ctx, "tcr_duration: n_level * (n_bin + 1) must be <= 64");
     return 0;
 }
 
@@ -166,12 +127,12 @@ hipError_t duration_launch(const DuCall &d, const ScanRows<WfRec> &rows, const S
     pol.wind = wind_scan<UNIT_C>(d.prm);
     for (int l = 0; l < NL; ++l) {
         pol.level[l] = l < d.n_level ? d.levels[l] : INFINITY;
-        pol.site_level[l] = (d.site_hours && l < d.n_level) ? d.site_hours[l] : nullptr;
+        pol.out.plane[l] = (d.site_hours && l < d.n_level) ? d.site_hours[l] : nullptr;
     }
     pol.unit = d.prm->dt_s / (7200.0 * d.prm->substeps);
-    pol.n_level = d.n_level; pol.n_hbin = d.n_bin;
+    pol.out.n_row = d.n_level; pol.out.n_hbin = d.n_bin;
     pol.level_part = d.level_part;
-    return wind_scan_launch(d.t, d.prm, rows, L, stage, pol);         // (the scan sees the footprint's rows as DuRec)
+    return wind_scan_launch(d.t, d.prm, rows, L, stage, pol);
 }
 
 }  // namespace
@@ -191,15 +152,14 @@ int tcr_duration_dev(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_para
     const int64_t n_rec = (t->n_t - 1) * prm->substeps + 1;
     const size_t n_stage = (size_t)std::max<int64_t>(1, t->n_trk * t->n_t);
     const DuCall d{t, prm, n_level, n_bin, levels, site_hours, level_part};
-    // (the modes of every NL have the one shape)
-    const int rc = scan_run<WfRec>(ctx, w, "tcr_duration", t, plan, ScanLevels<kDuMaxLevel>::shape(n_level, n_bin, thresholds), n_rec,
+    const int rc = scan_run<WfRec>(ctx, w, "tcr_duration", t, plan, ScanStack::shape(n_level, n_bin, 0, thresholds), n_rec,
                                    n_stage * sizeof(WfStage), n_site, site_lon, site_lat, prm->r_out_km, kWfEarthR / 1000.0, counts, nullptr,
                                    st, [&](const ScanRows<WfRec> &rows, const ScanLaunch &L, void *stage) {
         const bool unit = prm->ck_cd == 1.0, few = n_level <= 4;
         if (unit && few) return duration_launch<true, 4>(d, rows, L, stage);
-        if (unit) return duration_launch<true, kDuMaxLevel>(d, rows, L, stage);
+        if (unit) return duration_launch<true, kScanMaxRow>(d, rows, L, stage);
         if (few) return duration_launch<false, 4>(d, rows, L, stage);
-        return duration_launch<false, kDuMaxLevel>(d, rows, L, stage);
+        return duration_launch<false, kScanMaxRow>(d, rows, L, stage);
     });
     if (rc) return rc;
     if (half_steps) {
@@ -221,20 +181,16 @@ int tcr_duration_host(tcr_ctx *ctx, const tcr_wind_tracks *t, const tcr_wind_par
     DevBuf B;
     tcr_wind_tracks d;
     const ScanHostIO io = scan_host_io(B, t, n_site, site_lon, site_lat, n_level * n_bin, false);
-    const size_t n_half = (size_t)n_site * t->n_group * n_level, n_plane = (size_t)n_site * std::max<int64_t>(1, t->n_trk);
+    const size_t n_half = (size_t)n_site * t->n_group * n_level;
     int64_t *d_half = half_steps ? B.get<int64_t>(n_half) : nullptr;
-    double *d_hours[kDuMaxLevel] = {};
-    bool ok = wind_tracks_upload(B, t, &d) && io.ok && (!half_steps || d_half);
-    for (int l = 0; l < n_level && ok; ++l)
-        if (site_hours && site_hours[l]) ok = (d_hours[l] = B.get<double>(n_plane)) != nullptr;
-    if (!ok) return fail(ctx, "tcr_duration_host: device allocation / upload failed");
+    double *d_hours[kScanMaxRow] = {};
+    if (!wind_tracks_upload(B, t, &d) || !io.ok || (half_steps && !d_half) || !scan_host_planes(B, io, n_level, site_hours, d_hours))
+        return fail(ctx, "tcr_duration_host: device allocation / upload failed");
     if (tcr_duration_dev(ctx, &d, prm, n_site, io.site_lon, io.site_lat, n_level, levels, n_bin, thresholds, io.counts, d_half, d_hours,
                          ctx->stream))
         return -1;
     if (half_steps) HIPCHK(ctx, hipMemcpyAsync(half_steps, d_half, sizeof(int64_t) * n_half, hipMemcpyDeviceToHost, ctx->stream));
-    for (int l = 0; l < n_level; ++l)
-        if (d_hours[l] && io.n_max)
-            HIPCHK(ctx, hipMemcpyAsync(site_hours[l], d_hours[l], sizeof(double) * io.n_max, hipMemcpyDeviceToHost, ctx->stream));
+    if (scan_download_planes(ctx, io, n_level, site_hours, d_hours)) return -1;
     return scan_download(ctx, io, counts, nullptr);
 }
 

@@ -26,16 +26,17 @@ namespace {
 constexpr int kRfMaxSub = 64;
 
 // one sample or sub-sample (128 bytes): half-angle terms of the centre (distance), full-angle terms (the cap's centre), the
-// profile in mm/h and km, and the weight in hours; then pad0 and pad1, which k_rain_prep fills with the record's index in its
-// track and whether it is the track's last (int64 in the slots' bits).  uniform() does not load them: only the accumulation
-// windows read them (AcRec, tcr_accumulation.hip)
+// profile in mm/h and km, and the weight in hours; then q and end, the record's index in its track and whether it is the track's
+// last, which k_rain_prep fills and only the accumulation windows read (tcr_accumulation.hip)
 struct RfRec {
-    double sp, cp, sl, cl, cosp, t0, slope, tm, rm, ire, w, sinp, sinl, cosl, pad0, pad1;
+    double sp, cp, sl, cl, cosp, t0, slope, tm, rm, ire, w, sinp, sinl, cosl;
+    int64_t q, end;
     static __device__ __forceinline__ RfRec uniform(const RfRec *p)
     {
         const double *d = &p->sp;
         return RfRec{hz_uniform(d), hz_uniform(d + 1), hz_uniform(d + 2), hz_uniform(d + 3), hz_uniform(d + 4), hz_uniform(d + 5),
-                     hz_uniform(d + 6), hz_uniform(d + 7), hz_uniform(d + 8), hz_uniform(d + 9), hz_uniform(d + 10), 0.0, 0.0, 0.0, 0.0, 0.0};
+                     hz_uniform(d + 6), hz_uniform(d + 7), hz_uniform(d + 8), hz_uniform(d + 9), hz_uniform(d + 10), 0.0, 0.0, 0.0,
+                     hz_uniform(&p->q), hz_uniform(&p->end)};
     }
     __device__ void centre(HzCap *out) const { out->x = cosp * cosl; out->y = cosp * sinl; out->z = sinp; }
 };
@@ -64,7 +65,7 @@ __device__ __forceinline__ RfRec rf_record(const RfPrepArgs &a, double x, double
     r.slope = (r.tm - r.t0) / r.rm;
     r.ire = 1.0 / (a.a[3] + a.b[3] * u);
     r.w = w;
-    r.pad0 = r.pad1 = 0.0;
+    r.q = r.end = 0;
     return r;
 }
 
@@ -83,8 +84,8 @@ __device__ __forceinline__ RfRec rf_sub_record(const RfPrepArgs &a, const double
         dl -= 360.0 * floor((dl + 180.0) / 360.0);      // [-180, 180)
         r = rf_record(a, x + tau * dl, y + tau * (lat[k + 1] - y), v + tau * (vv[k + 1] - v), w);
     }
-    r.pad0 = __longlong_as_double(q);                   // (AcRec, tcr_accumulation.hip)
-    r.pad1 = __longlong_as_double(q == nr - 1 ? 1 : 0);
+    r.q = q;
+    r.end = q == nr - 1 ? 1 : 0;
     return r;
 }
 

@@ -7,9 +7,11 @@
 //   counts[site][group][bin] = #storms of the group with site_max >= thr[bin]
 //
 // An analysis supplies
-//   a record type   plain doubles that begin with the half-angle terms { sp, cp, sl, cl, cosp } of the point (the distance test),
-//                   with  static Rec uniform(const Rec *)  (the terms a pair reads, through scalar loads)  and
-//                   void centre(HzCap *) const  (the unit vector of the point, for a cap centred on it);
+//   a record type   8-byte slots that begin with the half-angle terms { sp, cp, sl, cl, cosp } of the point (the distance test):
+//                   doubles, and int64 for what a prep kernel counts (a half-weight, a record's index), with
+//                   static Rec uniform(const Rec *)  (every slot a policy may read, through scalar loads: one that the running
+//                   policy does not read is dead code)  and  void centre(HzCap *) const  (the unit vector of the point, for a
+//                   cap centred on it);
 //   a prep kernel   one wave per storm: writes the storm's records to the front of its row and ends with scan_finish_row
 //                   (NaN padding of the last segment, record count, bounding caps of the storm and of every kHzSeg-record segment);
 //   a policy        { Rec, Mode, kUnroll, value(site, record, a) and whatever else its mode calls }: a compile-time type that
@@ -26,8 +28,11 @@
 //                                                      per-storm outputs and the storm's place in the lane's histogram;
 //                     end_chunk(pol, lane)             the lane's n_cell partial counts of this chunk, and its per-chunk totals;
 //                     on the host  a ScanShape: the partial counts of a (chunk, site), the LDS bytes of a wave, the thresholds.
-//                   ScanPeak<false> (max) and ScanPeak<true> (sum in record order) are here; a mode only one analysis has is in
-//                   that analysis's file, with its own argument for what follows.
+//                   Here: ScanStack, the histogram of up to kScanMaxRow values per storm, each with an optional plane and
+//                   (n_hbin + 1) cells of its own, and on it ScanPeak<false> (max) and ScanPeak<true> (sum in record order), its
+//                   one-row case.  A mode only one analysis has is in that analysis's file, with its own argument for what
+//                   follows: LossMode (tcr_loss.hip, on ScanPeak), ScanJoint (tcr_compound.hip), and on ScanStack ScanLevels
+//                   (tcr_duration.hip) and ScanWindows (tcr_accumulation.hip).
 // and calls scan_run with a ScanPlan and a workspace of its own (ScanWs, one instance per user in tcr_ctx: calls of different
 // analyses may be in flight on different streams of one context).
 //
@@ -67,13 +72,6 @@ struct ScanRows {
     HzCap *storm;                           // [n_trk]
     int32_t *cnt;                           // [n_trk] records
     int64_t n_seg_max;
-    // the same rows through another record type of the same layout
-    template <class Rec2>
-    ScanRows<Rec2> as() const
-    {
-        static_assert(sizeof(Rec2) == sizeof(Rec), "a view of the rows keeps the record's size");
-        return ScanRows<Rec2>{reinterpret_cast<Rec2 *>(rec), seg, storm, cnt, n_seg_max};
-    }
 };
 
 // one site's terms: half angles (distance), full angles (direction); a policy's value() reads what it needs, the rest is dead code
@@ -152,17 +150,61 @@ __device__ __forceinline__ int scan_rank(const double *thr, int n, double m)
     return lo;
 }
 
+constexpr int kScanMaxRow = 8;              // rows of a stacked histogram: the per-row accumulators of a mode on it
+
+// where the rows of a stacked histogram go: launch-uniform, embedded in the policy of a mode on ScanStack (N accumulators, the
+// call's n_row <= N)
+template <int N>
+struct ScanStackOut {
+    static_assert(N >= 1 && N <= kScanMaxRow, "a stacked mode has 1 to kScanMaxRow row accumulators");
+    int32_t n_row, n_hbin;
+    double *plane[N];                       // [n_site][n_trk] each, or NULL
+};
+
+// The histogram tail of a mode with up to kScanMaxRow values per storm (rows: levels, windows), all ranked against the one list of
+// n_hbin thresholds in thr: cells [n_row][n_hbin + 1][64] of int32, the storms of this lane whose value of the row passes exactly
+// k thresholds; partial counts [row][threshold], n_cell = n_row n_hbin, which k_hazard_reduce sums unchanged.  A mode keeps its
+// values in fixed arrays and calls finish under `#pragma unroll` / `if (row < n_row)`, so that they stay registers.
+struct ScanStack {
+    static ScanShape shape(int32_t n_row, int32_t n_hbin, size_t extra_lds_bytes, const double *thr)
+    {
+        return ScanShape{n_row * n_hbin, sizeof(int32_t) * 64 * (size_t)n_row * (n_hbin + 1) + extra_lds_bytes, n_hbin, thr};
+    }
+    static __device__ __forceinline__ void begin(const ScanLane &c, int n_row, int n_hbin)
+    {
+        for (int k = 0; k < n_row * (n_hbin + 1); ++k) c.lds[k * 64 + c.lane] = 0;
+    }
+    static __device__ __forceinline__ void count(const ScanLane &c, int row, int n_hbin, double v)
+    {
+        c.lds[(row * (n_hbin + 1) + scan_rank(c.a.thr, n_hbin, v)) * 64 + c.lane] += 1;
+    }
+    // a row of storm s: the lane that accumulated v writes it to the row's plane; with `any` (the storm has an included record)
+    // it is counted
+    template <int N>
+    static __device__ __forceinline__ void finish(const ScanStackOut<N> &o, const ScanLane &c, int row, int64_t s, bool any, double v)
+    {
+        if (o.plane[row] && c.valid) o.plane[row][c.site * c.a.n_trk + s] = v;
+        if (any) count(c, row, o.n_hbin, v);
+    }
+    static __device__ __forceinline__ void end_chunk(const ScanLane &c, int n_row, int n_hbin)    // exactly k -> at least b + 1, per row
+    {
+        if (!c.valid) return;
+        int32_t *out = c.a.part + (c.chunk * c.a.n_site + c.site) * c.a.n_cell;
+        for (int r = 0; r < n_row; ++r) {
+            int32_t n = 0;
+            for (int b = n_hbin - 1; b >= 0; --b) { n += c.lds[(r * (n_hbin + 1) + b + 1) * 64 + c.lane]; out[r * n_hbin + b] = n; }
+        }
+    }
+};
+
 // The mode of a peak: the max of value over a storm's included records, or with SUM their sum in record order (the first included
-// record replaces the NaN start, every later one is added to it: nothing is ever added to a NaN), to site_max; cells
-// [n_bin + 1][64] of int32, the storms of this lane whose value passes exactly k thresholds.
+// record replaces the NaN start, every later one is added to it: nothing is ever added to a NaN), to site_max; the one-row
+// ScanStack with n_hbin = n_cell.
 template <bool SUM>
 struct ScanPeak {
     struct Storm { double m = NAN; };
-    static ScanShape shape(int32_t n_bin, const double *thr) { return ScanShape{n_bin, sizeof(int32_t) * 64 * (n_bin + 1), n_bin, thr}; }
-    template <class P> __device__ __forceinline__ void begin(const P &, const ScanLane &c)
-    {
-        for (int k = 0; k <= c.a.n_cell; ++k) c.lds[k * 64 + c.lane] = 0;
-    }
+    static ScanShape shape(int32_t n_bin, const double *thr) { return ScanStack::shape(1, n_bin, 0, thr); }
+    template <class P> __device__ __forceinline__ void begin(const P &, const ScanLane &c) { ScanStack::begin(c, 1, c.a.n_cell); }
     template <class P, class Rec> __device__ __forceinline__ void add(const P &pol, Storm &st, const ScanSite &me, const Rec &p, double q)
     {
         if constexpr (SUM) { const double v = pol.value(me, p, q); st.m = isnan(st.m) ? v : st.m + v; }     // in record order
@@ -175,20 +217,14 @@ struct ScanPeak {
     }
     __device__ __forceinline__ void count(const ScanLane &c, double m)
     {
-        if (!isnan(m)) c.lds[scan_rank(c.a.thr, c.a.n_cell, m) * 64 + c.lane] += 1;
+        if (!isnan(m)) ScanStack::count(c, 0, c.a.n_cell, m);
     }
     template <class P> __device__ __forceinline__ void end_storm(const P &, const ScanLane &c, const Storm &st, int64_t s, bool)
     {
         store(c, s, st.m);
         count(c, st.m);
     }
-    template <class P> __device__ __forceinline__ void end_chunk(const P &, const ScanLane &c)           // exactly k -> at least b + 1
-    {
-        if (!c.valid) return;
-        int32_t n = 0;
-        int32_t *out = c.a.part + (c.chunk * c.a.n_site + c.site) * c.a.n_cell;
-        for (int b = c.a.n_cell - 1; b >= 0; --b) { n += c.lds[(b + 1) * 64 + c.lane]; out[b] = n; }
-    }
+    template <class P> __device__ __forceinline__ void end_chunk(const P &, const ScanLane &c) { ScanStack::end_chunk(c, 1, c.a.n_cell); }
 };
 
 // The track of a prep kernel (one wave): the number of samples before the first j in [0, n_t) with bad(j), n_t when there is none.
@@ -228,7 +264,9 @@ __device__ void scan_finish_row(const ScanRows<Rec> &o, int64_t s, int n)
 {
     const int lane = threadIdx.x;
     Rec *row = o.rec + s * o.n_seg_max * kHzSeg;
-    // the rest of the last segment: records no distance test passes (NaN terms), so that every segment is kHzSeg records long
+    // the rest of the last segment: records no distance test passes (NaN terms), so that every segment is kHzSeg records long.
+    // Written slot by slot as doubles, so a record's int64 slots hold NaN bits: no pair of a padding record is included, and no
+    // mode reads a record outside add
     Rec pad;
     for (size_t i = 0; i < sizeof(Rec) / sizeof(double); ++i) reinterpret_cast<double *>(&pad)[i] = NAN;
     for (int j = n + lane; j < (n + kHzSeg - 1) / kHzSeg * kHzSeg; j += 64) row[j] = pad;
@@ -331,6 +369,14 @@ int scan_check(tcr_ctx *ctx, const char *who, const Tracks *t, int64_t n_t_max, 
     if (t->group_off[0] != 0 || t->group_off[t->n_group] != t->n_trk) return fail(ctx, "%s: group_off must run from 0 to n_trk", who);
     for (int32_t g = 0; g < t->n_group; ++g)
         if (t->group_off[g + 1] < t->group_off[g]) return fail(ctx, "%s: group_off must not decrease", who);
+    return 0;
+}
+
+// the rows of a call on ScanStack; row: their name in the entry point's arguments ("level": n_level)
+inline int scan_stack_check(tcr_ctx *ctx, const char *who, const char *row, int32_t n_row, int32_t n_bin)
+{
+    if (n_row < 1 || n_row > kScanMaxRow) return fail(ctx, "%s: n_%s must be in [1, 8]", who, row);
+    if ((int64_t)n_row * ((int64_t)n_bin + 1) > kHzMaxBin) return fail(ctx, "%s: n_%s * (n_bin + 1) must be <= 64", who, row);
     return 0;
 }
 
@@ -461,7 +507,7 @@ struct ScanHostIO {
     const double *site_lon, *site_lat;
     int32_t *counts;
     double *site_max;
-    size_t n_out, n_max;
+    size_t n_out, n_max, n_plane;           // n_max: values of a [n_site][n_trk] plane; n_plane: what is allocated for one (>= 1)
     bool ok;
 };
 
@@ -472,10 +518,30 @@ ScanHostIO scan_host_io(DevBuf &B, const Tracks *t, int64_t n_site, const double
     ScanHostIO d{};
     d.site_lon = B.put(site_lon, (size_t)n_site); d.site_lat = B.put(site_lat, (size_t)n_site);
     d.n_out = (size_t)n_site * t->n_group * n_cell; d.n_max = (size_t)n_site * t->n_trk;
+    d.n_plane = (size_t)n_site * std::max<int64_t>(1, t->n_trk);
     d.counts = B.get<int32_t>(d.n_out);
-    d.site_max = want_max ? B.get<double>((size_t)n_site * std::max<int64_t>(1, t->n_trk)) : nullptr;
+    d.site_max = want_max ? B.get<double>(d.n_plane) : nullptr;
     d.ok = d.site_lon && d.site_lat && d.counts && (!want_max || d.site_max);
     return d;
+}
+
+// The further optional [n_site][n_trk] planes of a _host entry point, host[0 .. n) (host itself may be NULL): dev[i] is a plane of
+// B for every host[i] that is not NULL, else NULL.  false: an allocation failed.
+inline bool scan_host_planes(DevBuf &B, const ScanHostIO &d, int n, double *const *host, double **dev)
+{
+    for (int i = 0; i < n; ++i) {
+        dev[i] = nullptr;
+        if (host && host[i] && !(dev[i] = B.get<double>(d.n_plane))) return false;
+    }
+    return true;
+}
+
+// their way back, enqueued on the context's stream: before scan_download, which waits for it
+inline int scan_download_planes(tcr_ctx *ctx, const ScanHostIO &d, int n, double *const *host, double *const *dev)
+{
+    for (int i = 0; i < n; ++i)
+        if (dev[i] && d.n_max) HIPCHK(ctx, hipMemcpyAsync(host[i], dev[i], sizeof(double) * d.n_max, hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
 }
 
 int scan_download(tcr_ctx *ctx, const ScanHostIO &d, int32_t *counts, double *site_max)

@@ -33,16 +33,18 @@ constexpr double kWfOmega = 7.292e-5;               // s^-1
 
 struct WfStage { double lon, lat, v, rm, ae, an, pad0, pad1; };      // one track sample (64 bytes)
 // one sample or sub-sample (128 bytes): half-angle terms of the centre (distance), full-angle terms (direction), rm (m), Mm, f / 2,
-// 1 + |A / v|^2 and b = 2 h A / v; then hw, which k_wind_prep fills with the record's trapezoid half-weight (an int64 in the slot's
-// bits: 2, or 1 for a track's first and last record) and only tcr_duration.hip reads: uniform() does not load it
+// 1 + |A / v|^2 and b = 2 h A / v; then hw, the record's trapezoid half-weight (2, or 1 for a track's first and last record),
+// which k_wind_prep fills and only tcr_duration.hip reads
 struct WfRec {
-    double sp, cp, sl, cl, cosp, sinp, sinl, cosl, rm, mm, f2, a2, be, bn, hw, pad1;
+    double sp, cp, sl, cl, cosp, sinp, sinl, cosl, rm, mm, f2, a2, be, bn;
+    int64_t hw;
+    double pad1;
     static __device__ __forceinline__ WfRec uniform(const WfRec *p)
     {
         const double *d = &p->sp;
         return WfRec{hz_uniform(d), hz_uniform(d + 1), hz_uniform(d + 2), hz_uniform(d + 3), hz_uniform(d + 4), hz_uniform(d + 5),
                      hz_uniform(d + 6), hz_uniform(d + 7), hz_uniform(d + 8), hz_uniform(d + 9), hz_uniform(d + 10), hz_uniform(d + 11),
-                     hz_uniform(d + 12), hz_uniform(d + 13), 0.0, 0.0};
+                     hz_uniform(d + 12), hz_uniform(d + 13), hz_uniform(&p->hw), 0.0};
     }
     __device__ void centre(HzCap *out) const { out->x = cosp * cosl; out->y = cosp * sinl; out->z = sinp; }
 };
@@ -97,7 +99,7 @@ __device__ __forceinline__ WfRec wf_record(double x, double y, double v, double 
     r.sp = sin(hp); r.cp = cos(hp); r.sl = sin(hl); r.cl = cos(hl);
     r.cosp = cos(phi); r.sinp = sin(phi); r.sinl = sin(lam); r.cosl = cos(lam);
     r.rm = rm_km * 1000.0;
-    r.hw = r.pad1 = 0.0;
+    r.hw = 0; r.pad1 = 0.0;
     if (v > 0.0) {
         const double f2 = kWfOmega * fabs(r.sinp);          // f / 2
         const double h2 = y >= 0.0 ? 2.0 : -2.0;            // 2 h
@@ -165,7 +167,7 @@ __global__ __launch_bounds__(64) void k_wind_prep(WfPrepArgs a)
     __syncthreads();                                    // the records read stage entries other lanes wrote
     for (int q = lane; q < nr; q += 64) {
         WfRec r = wf_sub_record(st, q, a.sub);
-        r.hw = __longlong_as_double(q == 0 || q == nr - 1 ? 1 : 2);
+        r.hw = q == 0 || q == nr - 1 ? 1 : 2;
         row[q] = r;
     }
     scan_finish_row(a.out, s, nr);
@@ -226,13 +228,12 @@ inline WfPrepArgs wind_prep_args(const tcr_wind_tracks *t, const tcr_wind_params
 template <bool UNIT_C>
 WindScan<UNIT_C> wind_scan(const tcr_wind_params *prm) { return WindScan<UNIT_C>{prm->ck_cd, 2.0 - prm->ck_cd, 1.0 / (2.0 - prm->ck_cd)}; }
 
-// The launch step of scan_run for every analysis on the footprint's records: the footprint's prep kernel, then Policy's scan, which
-// may read the rows through a record type of its own with WfRec's layout.
+// The launch step of scan_run for every analysis on the footprint's records: the footprint's prep kernel, then Policy's scan.
 template <typename Policy>
 hipError_t wind_scan_launch(const tcr_wind_tracks *t, const tcr_wind_params *prm, const ScanRows<WfRec> &rows, const ScanLaunch &L,
                             void *stage, const Policy &pol)
 {
-    return scan_launch(k_wind_prep, wind_prep_args(t, prm, stage, rows), rows.template as<typename Policy::Rec>(), L, pol);
+    return scan_launch(k_wind_prep, wind_prep_args(t, prm, stage, rows), rows, L, pol);
 }
 
 // What a _host entry point checks and a _dev one cannot report: the rmax_km plane (when given) is finite and > 0 at every sample

@@ -28,7 +28,7 @@ import sys
 import numpy as np
 
 from . import _lib, analysis, hazard, windfield
-from .sitescan import site_scan
+from . import sitescan
 
 MAX_LEVELS = 8
 MAX_CELLS = 64
@@ -56,15 +56,10 @@ def site_duration(lon, lat, v, env, groups, site_lon, site_lat, dt_s, levels=DEF
     lev, want = _check_levels(levels, thresholds, return_hours)
     res, fl = _scan(lon, lat, v, env, groups, site_lon, site_lat, dt_s, lev, thresholds, rmax_km, ck_cd, r_out_km, substeps, want,
                     engine, device, n_groups)
+    planes = res.pop('planes')
     if return_hours is not False and return_hours is not None:
-        planes = res.pop('planes')
-        n_site, n_trk = int(res['counts'].shape[0]), int(lon.shape[0]) if hasattr(lon, 'shape') else len(lon)
-        out = fl.new((lev.size, n_site, n_trk), 'f8')
-        for l in range(lev.size):
-            out[l] = planes[l] if l in planes else np.nan
-        res['site_hours'] = out
-    else:
-        res.pop('planes')
+        n_trk = int(lon.shape[0]) if hasattr(lon, 'shape') else len(lon)
+        res['site_hours'] = sitescan.stacked_planes(fl, planes, lev.size, int(res['counts'].shape[0]), n_trk)
     return res
 
 
@@ -80,41 +75,21 @@ def _check_levels(levels, thresholds, return_hours):
         raise ValueError('thresholds must be finite, > 0 and strictly ascending')
     if lev.size * (thr.size + 1) > MAX_CELLS:
         raise ValueError('n_level * (n_bin + 1) must be <= %d' % MAX_CELLS)
-    if return_hours is True:
-        want = list(range(lev.size))
-    elif return_hours is False or return_hours is None:
-        want = []
-    else:
-        try:
-            want = sorted({int(l) for l in return_hours if int(l) == l and not isinstance(l, bool)})
-            if len(want) != len(list(return_hours)):
-                raise ValueError
-        except (TypeError, ValueError):
-            raise ValueError('return_hours must be True, False or a list of distinct level indices')
-        if any(not 0 <= l < lev.size for l in want):
-            raise ValueError('return_hours names a level that does not exist')
-    return lev, want
+    return lev, sitescan.wanted_rows(return_hours, lev.size, 'return_hours', 'level')
 
 
 def _scan(lon, lat, v, env, groups, site_lon, site_lat, dt_s, lev, thresholds, rmax_km, ck_cd, r_out_km, substeps, want, engine, device,
           n_groups):
     """One call of tcr_duration_*: (dict with ``planes`` = {level index: [n_site][n_trk] plane} for the levels in want, Flavour)."""
     planes, fl, thr, prm = windfield._prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
-    n_level, n_bin = int(lev.size), int(thr.size)
-    outputs = [('half_steps', ('site_group', n_level))] + [('hours%d' % l, 'pair') for l in want]
+    n_level = int(lev.size)
 
-    def make_args(a):
+    def make_args(a, hours):
         n_bin_, thr_, counts_, _ = a.out
-        hours = (C.c_void_p * n_level)()
-        for l, p in zip(want, a.outputs[1:]):
-            hours[l] = p
         return (C.byref(windfield._tracks_struct(a)), C.byref(prm)) + a.sites + \
-            (n_level, lev.ctypes.data_as(_lib.DP), n_bin_, thr_, counts_, a.outputs[0], hours if want else None)
-    res = site_scan('tcr_duration', planes, fl, groups, n_groups, site_lon, site_lat, thr, False, engine, device, make_args,
-                    more_outputs=outputs, count_cells=n_level * n_bin)
-    n_site, n_grp = int(res['counts'].shape[0]), int(res['counts'].shape[1])
-    res['counts'] = res['counts'].reshape(n_site, n_grp, n_level, n_bin)
-    res['planes'] = {l: res.pop('hours%d' % l) for l in want}
+            (n_level, lev.ctypes.data_as(_lib.DP), n_bin_, thr_, counts_, a.outputs[0], hours)
+    res = sitescan.stacked_scan('tcr_duration', planes, fl, groups, n_groups, site_lon, site_lat, thr, n_level, want, 'hours', engine,
+                                device, make_args, more_outputs=[('half_steps', ('site_group', n_level))])
     res['hours_per_half_step'] = hours_per_half_step(prm.dt_s, prm.substeps)
     res['levels'] = lev
     return res, fl
@@ -168,19 +143,15 @@ def main(argv=None):
     annual = res['half_steps'].sum(axis=1) * u / total_years
     more = {}
     if args.return_periods is not None:
-        from . import levels as rl
         lev = res['levels']
-        per_level = []
-        for l in range(lev.size):                           # one blocked pass per level, with that level's plane only
-            def one(t, x, y, l=l):
-                r, _ = _scan(t[0], t[1], t[2], t[3], groups, x, y, dt, lev, args.thresholds, kw['rmax_km'], kw['ck_cd'], kw['r_out_km'],
-                             kw['substeps'], [l], None, 0, total_years)
-                r['hours'] = r.pop('planes')[l]
-                return r
-            per_level.append(rl.device_levels(one, (lon, lat, v, tuple(env)), site_lon, site_lat, total_years, args.return_periods,
-                                              'hours', args.device))
-        more = dict(return_level=np.stack([r['return_level'] for r in per_level], axis=1), return_periods=per_level[0]['return_periods'],
-                    n_reach=per_level[0]['n_reach'])
+
+        def one(l, t, x, y):
+            r, _ = _scan(t[0], t[1], t[2], t[3], groups, x, y, dt, lev, args.thresholds, kw['rmax_km'], kw['ck_cd'], kw['r_out_km'],
+                         kw['substeps'], [l], None, 0, total_years)
+            r['value'] = r.pop('planes')[l]
+            return r
+        more = sitescan.stacked_return_levels(one, lev.size, (lon, lat, v, tuple(env)), site_lon, site_lat, total_years,
+                                              args.return_periods, args.device)
     rp = hazard.return_periods(res['counts'], total_years)
     np.savez(args.out, counts=res['counts'], return_period=rp, annual_hours=annual, levels=res['levels'], thresholds=res['thresholds'],
              site_lon=site_lon, site_lat=site_lat, total_years=total_years, dt_s=dt, **analysis.group_meta(args.tracks, gfile, gyear),

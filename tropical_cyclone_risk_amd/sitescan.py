@@ -1,6 +1,11 @@
-"""The Python side of the per-site scan (csrc/tcr_sitescan.h), which site hazard, wind footprint, portfolio loss, rainfall and
-compound hazard, wind duration and rain accumulation windows share: the checks of sites and groups, the order the kernel wants (the storms of a group next to each other, the
-sites in Z-order), the call, and the way back to the caller's site and storm order."""
+"""The Python side of the per-site scan (csrc/tcr_sitescan.h).
+
+Seven analyses share it: site hazard, wind footprint, portfolio loss, rainfall, compound hazard, wind duration and rain
+accumulation windows.  ``site_scan`` checks the sites and groups, puts both in the order the kernel wants (the storms of a group
+next to each other, the sites in Z-order), makes the call and maps every output back to the caller's site and storm order.
+
+The last two analyses count several values per storm, one per row (a wind level, a window length), each with an optional
+[n_site][n_trk] plane.  ``wanted_rows``, ``stacked_scan``, ``stacked_planes`` and ``stacked_return_levels`` are what they share."""
 import collections
 import ctypes as C
 
@@ -113,3 +118,61 @@ def site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, retu
     if return_max:
         res['site_max'] = by_pair(smax)
     return res
+
+
+def wanted_rows(value, n_row, arg_name, row_name):
+    """The sorted row indices whose planes a caller wants: all for True, none for False or None, else a list of distinct
+    indices below n_row.  arg_name and row_name ('return_hours', 'level') form the two ValueError messages."""
+    if value is True:
+        return list(range(n_row))
+    if value is False or value is None:
+        return []
+    try:
+        want = sorted({int(i) for i in value if int(i) == i and not isinstance(i, bool)})
+        if len(want) != len(list(value)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError('%s must be True, False or a list of distinct %s indices' % (arg_name, row_name))
+    if any(not 0 <= i < n_row for i in want):
+        raise ValueError('%s names a %s that does not exist' % (arg_name, row_name))
+    return want
+
+
+def stacked_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, n_row, want, prefix, engine, device, make_args,
+                 more_outputs=()):
+    """site_scan for an entry point with n_row values per storm: ``counts`` comes back as [n_site][n_groups][n_row][n_bin] and
+    ``planes`` as {row: [n_site][n_trk] plane} for the rows in want (their outputs are named prefix + row).
+    make_args(ScanArgs, rows): rows is the entry point's array of n_row plane pointers (NULL for a row not wanted), or None
+    when want is empty; ScanArgs.outputs holds those of more_outputs alone."""
+    n_bin, n_more = int(thr.shape[0]), len(more_outputs)
+
+    def args(a):
+        rows = (C.c_void_p * n_row)()
+        for i, p in zip(want, a.outputs[n_more:]):
+            rows[i] = p
+        return make_args(a._replace(outputs=a.outputs[:n_more]), rows if want else None)
+    res = site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, False, engine, device, args,
+                    more_outputs=list(more_outputs) + [('%s%d' % (prefix, i), 'pair') for i in want], count_cells=n_row * n_bin)
+    n_site, n_grp = int(res['counts'].shape[0]), int(res['counts'].shape[1])
+    res['counts'] = res['counts'].reshape(n_site, n_grp, n_row, n_bin)
+    res['planes'] = {i: res.pop('%s%d' % (prefix, i)) for i in want}
+    return res
+
+
+def stacked_planes(fl, planes, n_row, n_site, n_trk):
+    """[n_row][n_site][n_trk] from stacked_scan's ``planes``; all NaN for a row that is not among them."""
+    out = fl.new((n_row, n_site, n_trk), 'f8')
+    for i in range(n_row):
+        out[i] = planes[i] if i in planes else np.nan
+    return out
+
+
+def stacked_return_levels(scan_row, n_row, planes, site_lon, site_lat, total_years, return_periods, device):
+    """What --return-periods adds to the .npz of a stacked analysis: one blocked levels.device_levels pass per row, each with
+    that row's plane only, and ``return_level`` stacked to [n_site][n_row][T].  scan_row(i, planes, lon_block, lat_block): the
+    analysis's scan with row i's plane under 'value'."""
+    from . import levels
+    per_row = [levels.device_levels(lambda t, x, y, i=i: scan_row(i, t, x, y), planes, site_lon, site_lat, total_years,
+                                    return_periods, 'value', device) for i in range(n_row)]
+    return dict(return_level=np.stack([r['return_level'] for r in per_row], axis=1), return_periods=per_row[0]['return_periods'],
+                n_reach=per_row[0]['n_reach'])
