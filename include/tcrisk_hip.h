@@ -837,6 +837,49 @@ int tcr_duration_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_win
 /* (site, record) pairs the last tcr_duration_* call of this context evaluated after culling; waits for that call */
 int tcr_duration_pairs(tcr_ctx *ctx, int64_t *pairs);
 
+/* ---- directional wind: peak wind by compass sector at sites ------------------------------------------------------------- */
+/* replaces: nothing in the reference's code; the "from where" next to the footprint's "how strong": directional design wind
+ * speeds, onshore against offshore wind at a coast, wind-driven rain on a facade, the exposure of a line or a runway.  The
+ * footprint's wind vector is formed once per (site, record) pair and its speed goes to the maximum of the compass sector it blows
+ * from, for up to 8 equal sectors at once.
+ *   track, records, sub-steps, inclusion and the wind of a (site, record) pair: those of the wind footprint above, bit for bit.
+ *   h               +1 for a centre latitude >= 0, -1 otherwise (from the sign of the record's sin lat: latitudes in
+ *                   (-28 * 2^-1074, 0), whose radians round to zero, take +1).
+ *   d, g, w         (d_e, d_n) = (e, n) / |(e, n)|, the footprint's own e and n: the unit bearing from the centre to the site.
+ *                   g_e = h (-d_n + be / 2), g_n = h (d_e + bn / 2) with b = 2 h A / v;  w = V (g_e, g_n).  |w| is the footprint's
+ *                   double, V sqrt(1 + |A / v|^2 + d_e b_n - d_n b_e), the one tcr_windfield_* takes the max of.
+ *   theta           the bearing of (-w_e, -w_n) in degrees clockwise from north, in [0, 360): the direction the wind blows from.
+ *   sectors         n_sector equal sectors of W = 360 / n_sector degrees, 1 <= n_sector <= 8; sector k holds the pairs with
+ *                   theta - sector0_deg in [(k - 1/2) W, (k + 1/2) W) mod 360.  With n_sector = 8 and sector0_deg = 0: 0 N, 1 NE,
+ *                   2 E, ... 7 NW.  A pair with |w| == 0 (the site on the centre, where (e, n) = 0; the profile clamped at 0 far
+ *                   out; v <= 0) has no sector and adds nothing.  The sector is decided from the signs of the cross products of
+ *                   (-w_e, -w_n) with the boundaries' unit vectors, not from a rounded angle: a pair within rounding of a
+ *                   boundary falls to one of its two sectors, and every other pair to its own.
+ *   site_dir_max    a host array of n_sector device pointers (host pointers in tcr_directional_host); the array may be NULL, and so
+ *                   may any entry (not written).  Entry k is a [n_site][n_trk] plane: max(0, max of |w| over the storm's included
+ *                   pairs of sector k); NaN in every sector where no record of the storm is included at the site, 0.0 in a sector
+ *                   no wind came from (the storm reached the site and did not exceed there).  The max over the sectors is
+ *                   tcr_windfield_*'s site_max bit for bit; with n_sector = 1 the plane is site_max.
+ *   counts          [n_site][n_group][n_sector][n_bin] (int32): storms s in [group_off[g], group_off[g + 1]) with
+ *                   site_dir_max[k] >= thresholds[b].  A NaN counts nowhere.
+ * Arguments: tracks and prm under exactly the rules of tcr_windfield_*; 1 <= n_sector <= 8; sector0_deg finite and in [0, 360);
+ * thresholds finite and strictly ascending; n_sector * (n_bin + 1) <= 64.  Every message begins with "tcr_directional:".  rm > 0 and
+ * finite at every sample of a track: tcr_directional_host checks the rmax_km plane as tcr_windfield_host does; tcr_directional_dev
+ * cannot, and drops a storm with a bad rm (NaN at every site and sector, counted nowhere).
+ * Results are maxima of per-pair values and integer counts: bit-identical from run to run, whatever the launch shape, the site
+ * order or the storm order.  _dev: planes, sites, counts and the planes site_dir_max points to are device memory, asynchronous on
+ * `stream`; thresholds, group_off and the site_dir_max pointer array are host memory in both entry points.  The workspace is the
+ * context's eighth: calls of tcr_directional_* on one context must be ordered, but one may be in flight next to a call of any
+ * other analysis on another stream. */
+int tcr_directional_dev(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_wind_params *prm, int64_t n_site, const double *site_lon,
+                        const double *site_lat, int32_t n_sector, double sector0_deg, int32_t n_bin, const double *thresholds,
+                        int32_t *counts, double *const *site_dir_max, void *stream);
+int tcr_directional_host(tcr_ctx *ctx, const tcr_wind_tracks *tracks, const tcr_wind_params *prm, int64_t n_site, const double *site_lon,
+                         const double *site_lat, int32_t n_sector, double sector0_deg, int32_t n_bin, const double *thresholds,
+                         int32_t *counts, double *const *site_dir_max);
+/* (site, record) pairs the last tcr_directional_* call of this context evaluated after culling; waits for that call */
+int tcr_directional_pairs(tcr_ctx *ctx, int64_t *pairs);
+
 /* ---- rain accumulation windows: peak D-hour rain depth at sites ------------------------------------------------------- */
 /* replaces: nothing in the reference's code; what lies between the rainfall footprint's two statistics.  The storm total is the
  * rain of a window longer than the track, the peak rate that of a window of no length; flood and drainage work needs the largest

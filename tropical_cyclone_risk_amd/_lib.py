@@ -45,6 +45,7 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_windfield_pairs', 'tcr_loss_dev', 'tcr_loss_host', 'tcr_rainfall_dev', 'tcr_rainfall_host', 'tcr_rainfall_pairs',
            'tcr_compound_dev', 'tcr_compound_host', 'tcr_compound_pairs', 'tcr_duration_dev', 'tcr_duration_host', 'tcr_duration_pairs',
            'tcr_accumulation_dev', 'tcr_accumulation_host', 'tcr_accumulation_pairs',
+           'tcr_directional_dev', 'tcr_directional_host', 'tcr_directional_pairs',
            'tcr_select_dev', 'tcr_select_host', 'tcr_tail_dev', 'tcr_tail_host', 'tcr_rowpack_count_dev', 'tcr_rowpack_fill_dev', 'tcr_rowpack_host',
            'tcr_probe_rhs_f32_host', 'tcr_integrate_steps_host', 'tcr_integrate_steps_f32_host')
 TCR_COMM_ID_BYTES = 128
@@ -313,6 +314,10 @@ def lib():
                                        C.c_int32, C.POINTER(C.c_int32), C.c_int32, DP, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
     L.tcr_accumulation_host.argtypes = L.tcr_accumulation_dev.argtypes[:-1]
     L.tcr_accumulation_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.tcr_directional_dev.argtypes = [C.c_void_p, C.POINTER(WindTracks), C.POINTER(WindParams), C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_int32, C.c_double, C.c_int32, DP, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
+    L.tcr_directional_host.argtypes = L.tcr_directional_dev.argtypes[:-1]
+    L.tcr_directional_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.tcr_select_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_void_p,
                                  C.c_void_p, C.c_void_p]
     L.tcr_select_host.argtypes = L.tcr_select_dev.argtypes[:-1]

@@ -1,5 +1,6 @@
 // The site scan: what the per-site analyses of a track ensemble share.  Its users: tcr_hazard.hip, tcr_windfield.hip,
-// tcr_loss.hip, tcr_rainfall.hip, tcr_compound.hip, tcr_duration.hip, tcr_accumulation.hip.  Each of them turns every storm into a row of wave-uniform
+// tcr_loss.hip, tcr_rainfall.hip, tcr_compound.hip, tcr_duration.hip, tcr_directional.hip, tcr_accumulation.hip.  Each of them turns every storm into a
+// row of wave-uniform
 // records, accumulates something per (site, storm) over the storm's records with haversine(site, record) <= R, and counts the
 // storms of every group by what was accumulated.  In the plainest form (ScanPeak below):
 //
@@ -32,7 +33,7 @@
 //                   (n_hbin + 1) cells of its own, and on it ScanPeak<false> (max) and ScanPeak<true> (sum in record order), its
 //                   one-row case.  A mode only one analysis has is in that analysis's file, with its own argument for what
 //                   follows: LossMode (tcr_loss.hip, on ScanPeak), ScanJoint (tcr_compound.hip), and on ScanStack ScanLevels
-//                   (tcr_duration.hip) and ScanWindows (tcr_accumulation.hip).
+//                   (tcr_duration.hip), ScanSectors (tcr_directional.hip) and ScanWindows (tcr_accumulation.hip).
 // and calls scan_run with a ScanPlan and a workspace of its own (ScanWs, one instance per user in tcr_ctx: calls of different
 // analyses may be in flight on different streams of one context).
 //

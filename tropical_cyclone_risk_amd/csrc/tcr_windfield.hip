@@ -11,7 +11,8 @@
 //                    sub-sample with every wave-uniform term a pair needs (and its trapezoid half-weight); the scan's row tail writes the bounding caps of the
 //                    storm and of every kHzSeg-record segment;
 //   WindScan<c == 1> the policy of k_site_scan: the scan tests the haversine argument a against a_out first (no trigonometry), so
-//                    only included lanes pay for asin, the square roots and the profile.
+//                    only included lanes pay for asin, the square roots and the profile.  from_angle is at_angle with the direction
+//                    the wind blows from (tcr_directional.hip).
 //
 // Per included pair (c: centre, s: site; the record holds the centre's terms):
 //   r = 2 R asin(sqrt(a))
@@ -198,6 +199,33 @@ struct WindScan {
         const double dd = e * e + nn * nn;
         const double cross = dd > 0.0 ? (e * p.bn - nn * p.be) / sqrt(dd) : 0.0;
         return V * sqrt(p.a2 + cross);
+    }
+    // The same with the direction the wind blows from (tcr_directional.hip).  The speed is at_angle's own expressions in at_angle's
+    // order (the build has no contraction), so it is at_angle's double bit for bit.  (fe, fn) = -sqrt(dd) (g_e, g_n) with
+    // g = h (-d_n + be / 2, d_e + bn / 2): a positive multiple of (-w_e, -w_n) wherever the speed is > 0, east and north.  h is the
+    // record's hemisphere sign from sinp: that is wf_record's `y >= 0` (-0.0 included) for every latitude whose radians are not
+    // rounded to zero, which leaves the 28 negative subnormals above -28 * 2^-1074 degrees.  dd == 0 (the site on the centre, where
+    // V = 0): no direction, and 0.
+    __device__ __forceinline__ double from_angle(const ScanSite &s, const WfRec &p, double ang, double &fe, double &fn) const
+    {
+        const double r = ang * kWfEarthR;
+        double V;
+        if (UNIT_C) {
+            V = r * (2.0 * p.mm / (p.rm * p.rm + r * r) - p.f2);
+        } else {
+            const double xr = r / p.rm, x2 = xr * xr;
+            V = r > 0.0 ? (p.mm * pow(2.0 * x2 / (two_c + c * x2), inv_exp) - p.f2 * (r * r)) / r : 0.0;
+        }
+        V = fmax(V, 0.0);
+        const double sdl = s.sinl * p.cosl - s.cosl * p.sinl, cdl = s.cosl * p.cosl + s.sinl * p.sinl;
+        const double e = s.cosp * sdl, nn = p.cosp * s.sinp - p.sinp * (s.cosp * cdl);
+        const double dd = e * e + nn * nn;
+        const double sd = sqrt(dd);
+        const double cross = dd > 0.0 ? (e * p.bn - nn * p.be) / sd : 0.0;
+        const double h = p.sinp >= 0.0 ? 1.0 : -1.0;
+        fe = h * (nn - 0.5 * p.be * sd);
+        fn = -h * (e + 0.5 * p.bn * sd);
+        return dd > 0.0 ? V * sqrt(p.a2 + cross) : 0.0;
     }
 };
 

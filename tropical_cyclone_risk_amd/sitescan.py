@@ -1,11 +1,13 @@
 """The Python side of the per-site scan (csrc/tcr_sitescan.h).
 
-Seven analyses share it: site hazard, wind footprint, portfolio loss, rainfall, compound hazard, wind duration and rain
-accumulation windows.  ``site_scan`` checks the sites and groups, puts both in the order the kernel wants (the storms of a group
-next to each other, the sites in Z-order), makes the call and maps every output back to the caller's site and storm order.
+Eight analyses share it: site hazard, wind footprint, portfolio loss, rainfall, compound hazard, wind duration, rain
+accumulation windows and directional wind.  ``site_scan`` checks the sites and groups, puts both in the order the kernel wants
+(the storms of a group next to each other, the sites in Z-order), makes the call and maps every output back to the caller's site
+and storm order.
 
-The last two analyses count several values per storm, one per row (a wind level, a window length), each with an optional
-[n_site][n_trk] plane.  ``wanted_rows``, ``stacked_scan``, ``stacked_planes`` and ``stacked_return_levels`` are what they share."""
+The last three analyses count several values per storm, one per row (a wind level, a window length, a compass sector), each with
+an optional [n_site][n_trk] plane.  ``wanted_rows``, ``stacked_scan``, ``stacked_planes`` and ``stacked_return_levels`` are what
+they share."""
 import collections
 import ctypes as C
 
