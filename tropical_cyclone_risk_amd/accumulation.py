@@ -36,7 +36,7 @@ from . import sitescan
 
 MAX_WINDOWS = 8
 MAX_WINDOW_SAMPLES = 96
-MAX_CELLS = 64
+MAX_CELLS = sitescan.MAX_CELLS
 MAX_LDS = 65536
 DEFAULT_WINDOWS_H = (6, 12, 24, 48, 72)
 
@@ -55,25 +55,18 @@ def site_accumulation(lon, lat, vmax, groups, site_lon, site_lat, dt_s, windows_
     NaN: no sample within r_out_km; all NaN for a window not asked for: a plane is n_site * n_trk * 8 bytes on the device, which
     is why they are selectable), in the type and on the device of ``lon``.
     """
-    win_h, m, want = _check_windows(windows_h, dt_s, thresholds, return_values)
-    res, fl = _scan(lon, lat, vmax, groups, site_lon, site_lat, dt_s, win_h, m, thresholds, r_out_km, substeps, coefficients, v_lo_kt,
-                    v_hi_kt, want, engine, device, n_groups)
-    planes = res.pop('planes')
-    if return_values is not False and return_values is not None:
-        n_trk = int(lon.shape[0]) if hasattr(lon, 'shape') else len(lon)
-        res['site_window'] = sitescan.stacked_planes(fl, planes, m.size, int(res['counts'].shape[0]), n_trk)
-    return res
+    scan = _bind(groups, dt_s, windows_h, thresholds, r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt, n_groups)
+    res, fl = scan((lon, lat, vmax), site_lon, site_lat, return_values, engine, device)
+    return sitescan.attach_planes(res, fl, 'site_window', return_values, lon)
 
 
 def _check_windows(windows_h, dt_s, thresholds, return_values):
     """The accumulation's own argument checks (ValueError): (windows_h, window_samples int32, the sorted window indices whose
     planes are wanted)."""
     try:
-        dt = float(dt_s)
-    except (TypeError, ValueError):
-        raise ValueError('dt_s must be finite and > 0')
-    if not (np.isfinite(dt) and dt > 0):
-        raise ValueError('dt_s must be finite and > 0')
+        dt = sitescan.check_dt(dt_s)
+    except (TypeError, ValueError):                         # (a dt_s that is no number at all gets the same text here)
+        raise ValueError(sitescan.BAD_DT)
     win_h = np.ascontiguousarray(np.asarray(windows_h, dtype=np.float64).reshape(-1))
     if not 1 <= win_h.size <= MAX_WINDOWS:
         raise ValueError('give 1 to %d windows' % MAX_WINDOWS)
@@ -86,9 +79,7 @@ def _check_windows(windows_h, dt_s, thresholds, return_values):
     if np.any(m < 1) or np.any(m > MAX_WINDOW_SAMPLES) or np.any(np.diff(m) <= 0):
         raise ValueError('windows must be positive, strictly ascending and at most %d samples long' % MAX_WINDOW_SAMPLES)
     m = np.ascontiguousarray(m.astype(np.int32))
-    thr = np.asarray(thresholds, dtype=np.float64).reshape(-1)
-    if thr.size < 1 or not np.isfinite(thr).all() or np.any(np.diff(thr) <= 0):
-        raise ValueError('thresholds must be finite and strictly ascending')
+    thr = sitescan.check_ascending(thresholds, sitescan.ASCENDING % 'thresholds')
     if m.size * (thr.size + 1) > MAX_CELLS:
         raise ValueError('n_window * (n_bin + 1) must be <= %d' % MAX_CELLS)
     if 512 * (int(m[-1]) + 1) + 256 * m.size * (thr.size + 1) > MAX_LDS:
@@ -96,24 +87,29 @@ def _check_windows(windows_h, dt_s, thresholds, return_values):
     return win_h, m, sitescan.wanted_rows(return_values, m.size, 'return_values', 'window')
 
 
-def _scan(lon, lat, vmax, groups, site_lon, site_lat, dt_s, win_h, m, thresholds, r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt,
-          want, engine, device, n_groups):
-    """One call of tcr_accumulation_*: (dict with ``planes`` = {window index: [n_site][n_trk] plane} for the windows in want,
-    Flavour)."""
-    planes, fl, thr, prm, _ = rainfall._prepare(lon, lat, vmax, dt_s, 'total', r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt,
-                                                thresholds, n_groups)
+def _bind(groups, dt_s, windows_h, thresholds, r_out_km=500., substeps=1, coefficients=None, v_lo_kt=35., v_hi_kt=155., n_groups=None):
+    """site_accumulation's arguments, checked as far as they stand alone (_check_windows) and bound into sitescan's
+    scan(tracks = (lon, lat, vmax), site_lon, site_lat, want, engine, device): one call of tcr_accumulation_*, whose ``planes`` are
+    those of the windows in want (a return_values).  rainfall._prepare needs the tracks: it runs in every call, after want's check."""
+    win_h, m, _ = _check_windows(windows_h, dt_s, thresholds, False)
     n_window = int(m.size)
 
-    def make_args(a, win):
-        lon_, lat_, vmax_ = a.planes
-        n_bin_, thr_, counts_, _ = a.out
-        return (C.byref(_lib.HazardTracks(lon=lon_, lat=lat_, vmax=vmax_, **a.tracks)), C.byref(prm)) + a.sites + \
-            (n_window, m.ctypes.data_as(C.POINTER(C.c_int32)), n_bin_, thr_, counts_, win)
-    res = sitescan.stacked_scan('tcr_accumulation', planes, fl, groups, n_groups, site_lon, site_lat, thr, n_window, want, 'window',
-                                engine, device, make_args)
-    res['windows_h'] = win_h
-    res['window_samples'] = m
-    return res, fl
+    def scan(tracks, site_lon, site_lat, want=(), engine=None, device=0):
+        want = sitescan.wanted_rows(want, n_window, 'return_values', 'window')
+        planes, fl, thr, prm, _ = rainfall._prepare(tracks, dt_s, 'total', r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt,
+                                                    thresholds, n_groups)
+
+        def make_args(a, win):
+            lon_, lat_, vmax_ = a.planes
+            n_bin_, thr_, counts_, _ = a.out
+            return (C.byref(_lib.HazardTracks(lon=lon_, lat=lat_, vmax=vmax_, **a.tracks)), C.byref(prm)) + a.sites + \
+                (n_window, m.ctypes.data_as(C.POINTER(C.c_int32)), n_bin_, thr_, counts_, win)
+        res = sitescan.stacked_scan('tcr_accumulation', planes, fl, groups, n_groups, site_lon, site_lat, thr, n_window, want, 'window',
+                                    engine, device, make_args)
+        res['windows_h'] = win_h
+        res['window_samples'] = m
+        return res, fl
+    return scan
 
 
 # ---------------------------------------------------------------------------------------------------------------- CLI
@@ -138,11 +134,7 @@ def parse_args(argv=None):
                    metavar='LO:HI:STEP', help='depths in mm (default: %s)' % ' '.join('%g' % t for t in DEFAULT_RAIN_THRESHOLDS))
     analysis.add_return_period_arg(p, 'the rain depth of every window (mm)')
     analysis.add_track_args(p, 'accumulation.npz')
-    a = p.parse_args(argv)
-    if a.tail_exceedances is not None:
-        p.error('--tail-exceedances is not offered for accumulation windows yet')
-    if not (a.site or a.sites or a.grid):
-        p.error('give sites with --site, --sites or --grid')
+    a = analysis.finish_parse(p, p.parse_args(argv), no_tail='--tail-exceedances is not offered for accumulation windows yet')
     if a.windows.size < 1 or not np.isfinite(a.windows).all() or np.any(a.windows <= 0) or np.any(np.diff(a.windows) <= 0) \
             or a.windows.size > MAX_WINDOWS:
         p.error('--windows: 1 to %d positive, strictly ascending window lengths in hours' % MAX_WINDOWS)
@@ -151,41 +143,28 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    site_lon, site_lat = analysis.collect_sites(args)
-    if site_lon.size == 0:
-        raise SystemExit('no sites')
-    lon, lat, vmax, groups, gfile, gyear, more = analysis.load_groups(args.tracks, extra=('time',))
-    dt = analysis.sample_spacing(more['time'])
-    total_years = len(gfile)
+    inp = analysis.load_inputs(args)
+    site_lon, site_lat, total_years = inp.site_lon, inp.site_lat, inp.total_years
+    tracks = (inp.lon, inp.lat, inp.vmax)
     try:
-        win_h, m, _ = _check_windows(args.windows, dt, args.thresholds, False)
+        scan = _bind(inp.groups, inp.dt_s, args.windows, args.thresholds, r_out_km=args.r_out_km, substeps=args.substeps,
+                     n_groups=total_years)
     except ValueError as e:
-        raise SystemExit('--windows / --thresholds at the files\' sample spacing of %g s: %s' % (dt, e))
-    kw = dict(r_out_km=args.r_out_km, substeps=args.substeps, n_groups=total_years)
-    res = site_accumulation(lon, lat, vmax, groups, site_lon, site_lat, dt, windows_h=win_h, thresholds=args.thresholds,
-                            device=args.device, **kw)
+        raise SystemExit('--windows / --thresholds at the files\' sample spacing of %g s: %s' % (inp.dt_s, e))
+    res, _ = scan(tracks, site_lon, site_lat, device=args.device)
+    win_h, m = res['windows_h'], res['window_samples']
     more = {}
     if args.return_periods is not None:
-        def one(i, t, x, y):
-            r, _ = _scan(t[0], t[1], t[2], groups, x, y, dt, win_h, m, args.thresholds, kw['r_out_km'], kw['substeps'], None, 35., 155.,
-                         [i], None, 0, total_years)
-            r['value'] = r.pop('planes')[i]
-            return r
-        more = sitescan.stacked_return_levels(one, m.size, (lon, lat, vmax), site_lon, site_lat, total_years, args.return_periods,
-                                              args.device)
+        more = sitescan.stacked_return_levels(scan, m.size, tracks, site_lon, site_lat, total_years, args.return_periods, args.device)
     rp = hazard.return_periods(res['counts'], total_years)
-    np.savez(args.out, counts=res['counts'], return_period=rp, windows_h=win_h, window_samples=m, thresholds=res['thresholds'],
-             site_lon=site_lon, site_lat=site_lat, total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps, dt_s=dt,
-             **analysis.group_meta(args.tracks, gfile, gyear), **more)
-    print('%d sites, %d storms, %d groups (%d files), total_years = %d, windows %s h, r_out = %g km, %d substeps -> %s'
-          % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, ','.join('%g' % w for w in win_h), args.r_out_km,
-             args.substeps, args.out))
+    analysis.save_npz(args, inp, dict(counts=res['counts'], return_period=rp, windows_h=win_h, window_samples=m,
+                                      thresholds=res['thresholds']), recorded=('r_out_km', 'substeps'), more=more)
+    analysis.print_summary(args, inp, ', windows %s h, r_out = %g km, %d substeps'
+                           % (','.join('%g' % w for w in win_h), args.r_out_km, args.substeps))
     if site_lon.size <= 10 and more:
-        print('rain depth (mm) by window (rows, hours) and return period (years): ' + ' '.join('%8g' % t for t in more['return_periods']))
-        for s in range(site_lon.size):
-            print('  site (%.4f, %.4f)' % (site_lon[s], site_lat[s]))
-            for i, w in enumerate(win_h):
-                print('    %6g h: ' % w + ' '.join('%8.4g' % x for x in more['return_level'][s, i]))
+        analysis.print_site_tables('rain depth (mm) by window (rows, hours) and return period (years): '
+                                   + ' '.join('%8g' % t for t in more['return_periods']), site_lon, site_lat,
+                                   ['%6g h: ' % w for w in win_h], more['return_level'], '%8.4g')
     return 0
 
 

@@ -1,7 +1,14 @@
-"""What the analyses of track files (hazard, landfall, climatology, windfield, loss, rainfall) share: NumPy-or-torch planes, the library
-context of one call, the group index of the storms, reading (file, year) groups from track files, and the pieces of their
-command lines.  The per-site scan they share on top of this is sitescan.py."""
+"""What the analyses of track files (hazard, landfall, climatology, windfield, loss, rainfall and those built on them) share:
+NumPy-or-torch planes, the library context of one call, the group index of the storms, reading (file, year) groups from track
+files, and their command lines.  The per-site scan they share on top of this is sitescan.py.
+
+A site analysis's command line is its own options plus five steps, one function each in the CLI section: ``finish_parse`` (what the
+options ask of each other, and that sites were given), ``load_inputs`` (sites and track planes as ``Inputs``), ``save_npz`` (the
+analysis's arrays and the tail every .npz has), ``print_summary`` (the one line on stdout) and ``print_site_rows`` /
+``print_site_tables`` (the per-site tables of up to 10 sites).  hazard, windfield and rainfall differ in the analysis alone:
+``threshold_main`` is the body of all three."""
 import argparse
+import collections
 import ctypes as C
 
 import numpy as np
@@ -10,6 +17,9 @@ from . import _lib
 
 DEFAULT_THRESHOLDS = np.arange(10, 81, 5).astype(np.float64)
 ENV_VARS = ('u250_trks', 'v250_trks', 'u850_trks', 'v850_trks')
+# what load_inputs returns: v and env are None without wind, dt_s without spacing; total_years is the number of groups
+Inputs = collections.namedtuple('Inputs', 'site_lon site_lat lon lat vmax v env groups gfile gyear dt_s total_years')
+SITE_ROW = '  site (%.4f, %.4f)'          # how every per-site line of a command line's tables begins
 
 
 # ------------------------------------------------------------------------------------------------------------- arrays
@@ -268,12 +278,6 @@ def add_return_period_arg(p, what):
                         'tail_threshold')
 
 
-def check_return_period_args(p, a):
-    """What the options of add_return_period_arg ask of each other, after parsing."""
-    if a.tail_exceedances is not None and a.return_periods is None:
-        p.error('--tail-exceedances needs --return-periods')
-
-
 def parse_floor(text):
     try:
         v = float(text)
@@ -289,14 +293,6 @@ def add_events_arg(p, what):
                    help='also write the event table: per site, the storms whose %s is at or above --events-min, with that value '
                         '(events.site_event_table; a pass of its own)' % what)
     p.add_argument('--events-min', type=parse_floor, default=None, metavar='V', help='the floor of --events-out (required with it)')
-
-
-def check_events_args(p, a):
-    """What the options of add_events_arg ask of each other, after parsing."""
-    if a.events_out is not None and a.events_min is None:
-        p.error('--events-out needs --events-min')
-    if a.events_min is not None and a.events_out is None:
-        p.error('--events-min needs --events-out')
 
 
 def read_sites_csv(fn):
@@ -325,10 +321,103 @@ def collect_sites(args):
     return np.array(lon, dtype=np.float64), np.array(lat, dtype=np.float64)
 
 
+def finish_parse(p, a, no_tail=None):
+    """What a site analysis's options ask of each other after parsing, in one order: those of add_return_period_arg (no_tail: the
+    analysis's sentence when it does not offer --tail-exceedances) and of add_events_arg where the parser has them, and that
+    sites were given.  Returns a."""
+    if getattr(a, 'tail_exceedances', None) is not None and (no_tail is not None or a.return_periods is None):
+        p.error(no_tail or '--tail-exceedances needs --return-periods')
+    if getattr(a, 'events_out', None) is not None and a.events_min is None:
+        p.error('--events-out needs --events-min')
+    if getattr(a, 'events_min', None) is not None and a.events_out is None:
+        p.error('--events-min needs --events-out')
+    if not (a.site or a.sites or a.grid):
+        p.error('give sites with --site, --sites or --grid')
+    return a
+
+
+def load_inputs(args, wind=False, spacing=True, sites=None):
+    """The parsed command line's inputs: the sites (sites: the caller's own (lon, lat); None: those of collect_sites, and
+    SystemExit without any), then the track files' planes through load_wind_planes (wind) or load_groups, with their sample
+    spacing where asked for."""
+    site_lon, site_lat = collect_sites(args) if sites is None else sites
+    if site_lon.size == 0:
+        raise SystemExit('no sites')
+    v = env = dt = None
+    if wind:
+        lon, lat, vmax, v, env, groups, gfile, gyear, dt = load_wind_planes(args.tracks)
+    elif spacing:
+        lon, lat, vmax, groups, gfile, gyear, more = load_groups(args.tracks, extra=('time',))
+        dt = sample_spacing(more['time'])
+    else:
+        lon, lat, vmax, groups, gfile, gyear = load_groups(args.tracks)
+    return Inputs(site_lon, site_lat, lon, lat, vmax, v, env, groups, gfile, gyear, dt, len(gfile))
+
+
+def save_npz(args, inp, arrays, recorded=(), more=()):
+    """Write args.out: the analysis's own arrays, then what every analysis saves (the sites, total_years, dt_s where the files'
+    spacing was read, group_meta) and the options among recorded ('r_out_km', 'substeps', 'rmax_km': NaN for None) as the command
+    line had them; more: the keys --return-periods adds."""
+    tail = dict(site_lon=inp.site_lon, site_lat=inp.site_lat, total_years=inp.total_years)
+    for name in recorded:
+        value = getattr(args, name)
+        tail[name] = np.nan if value is None else value
+    if inp.dt_s is not None:
+        tail['dt_s'] = inp.dt_s
+    np.savez(args.out, **arrays, **tail, **group_meta(args.tracks, inp.gfile, inp.gyear), **dict(more))
+
+
+def print_summary(args, inp, middle='', site_note=''):
+    """The line every command line prints after writing its .npz; middle: the analysis's own part, with its leading comma."""
+    print('%d sites%s, %d storms, %d groups (%d files), total_years = %d%s -> %s'
+          % (inp.site_lon.size, site_note, inp.lon.shape[0], inp.total_years, len(args.tracks), inp.total_years, middle, args.out))
+
+
+def print_site_rows(header, site_lon, site_lat, rows, fmt=None):
+    """One line per site under a header (None: none): the [n_site][k] numbers of rows, each through fmt, or with fmt None the
+    ready texts of rows."""
+    if header is not None:
+        print(header)
+    for i in range(site_lon.size):
+        print(SITE_ROW % (site_lon[i], site_lat[i]) + ': ' + (rows[i] if fmt is None else ' '.join(fmt % v for v in rows[i])))
+
+
+def print_site_tables(header, site_lon, site_lat, labels, tables, fmt):
+    """One small table per site under a header: the site's line, then a row of tables[site] per label."""
+    print(header)
+    for i in range(site_lon.size):
+        print(SITE_ROW % (site_lon[i], site_lat[i]))
+        for label, row in zip(labels, tables[i]):
+            print('    ' + label + ' '.join(fmt % x for x in row))
+
+
 def print_return_periods(thresholds, site_lon, site_lat, rp, unit='m/s'):
     """The return-period table of up to 10 sites (more: nothing).  unit: of the thresholds."""
-    if site_lon.size > 10:
-        return
-    print('return period (years) by threshold (%s): ' % unit + ' '.join('%6g' % t for t in thresholds))
-    for i in range(site_lon.size):
-        print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%6.3g' % v for v in rp[i]))
+    if site_lon.size <= 10:
+        print_site_rows('return period (years) by threshold (%s): ' % unit + ' '.join('%6g' % t for t in thresholds), site_lon,
+                        site_lat, rp, '%6.3g')
+
+
+def threshold_main(args, inp, block, tracks, key, unit='m/s', arrays=(), recorded=(), middle=''):
+    """What the command lines of hazard, windfield and rainfall do with their inputs, which is the same but for the analysis:
+    block(tracks, lon_block, lat_block, plane=False, device=0) is the analysis on some sites, with its per-storm plane (key, in
+    unit) when asked.  One plain call, or with --return-periods the blocked pass of levels.device_levels; the .npz (arrays: the
+    analysis's further keys), the summary line (middle), the tables, and with --events-out a pass of its own through the same block."""
+    from . import events, hazard, levels
+    with_plane = lambda t, x, y: block(t, x, y, plane=True)                                 # noqa: E731
+    more = {}
+    if args.return_periods is None:
+        res = block(tracks, inp.site_lon, inp.site_lat, device=args.device)
+    else:
+        res = levels.device_levels(with_plane, tracks, inp.site_lon, inp.site_lat, inp.total_years, args.return_periods, key,
+                                   args.device, tail_exceedances=args.tail_exceedances)
+        more = levels.npz_keys(res)
+    rp = hazard.return_periods(res['counts'], inp.total_years)
+    save_npz(args, inp, dict(counts=res['counts'], return_period=rp, thresholds=res['thresholds'], **dict(arrays)), recorded, more)
+    print_summary(args, inp, middle)
+    print_return_periods(res['thresholds'], inp.site_lon, inp.site_lat, rp, unit=unit)
+    if more:
+        levels.print_return_levels(res, inp.site_lon, inp.site_lat, unit=unit)
+    if args.events_out is not None:
+        events.write_cli_events(args, with_plane, tracks, inp.site_lon, inp.site_lat, key, unit, inp.groups, inp.gfile, inp.gyear)
+    return 0

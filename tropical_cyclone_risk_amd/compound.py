@@ -23,9 +23,8 @@ import sys
 import numpy as np
 
 from . import _lib, analysis, hazard, rainfall, windfield
-from .sitescan import site_scan
+from .sitescan import MAX_CELLS, site_scan          # MAX_CELLS bounds (n_wbin + 1) * (n_rbin + 1)
 
-MAX_CELLS = 64          # (n_wbin + 1) * (n_rbin + 1): the scan's histogram (kHzMaxBin)
 DEFAULT_WIND_THRESHOLDS = np.arange(20, 71, 10).astype(np.float64)                     # m/s
 DEFAULT_RAIN_THRESHOLDS = np.arange(50, 401, 50).astype(np.float64)                    # mm
 RAIN_KEY = {'total': 'site_rain', 'peak-rate': 'site_peak_rate'}
@@ -46,9 +45,9 @@ def site_compound(lon, lat, v, vmax, env, groups, site_lon, site_lat, dt_s, wind
     for bit windfield.site_wind's ``site_max`` and rainfall.site_rain's values where a storm's eight planes are finite as far as
     the planes either of them reads.
     """
-    wplanes, fl, wthr, wprm = windfield._prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, wind_r_out_km, substeps, wind_thresholds,
+    wplanes, fl, wthr, wprm = windfield._prepare((lon, lat, v, env), dt_s, rmax_km, ck_cd, wind_r_out_km, substeps, wind_thresholds,
                                                  n_groups)
-    rplanes, _, rthr, rprm, _ = rainfall._prepare(lon, lat, vmax, dt_s, stat, rain_r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt,
+    rplanes, _, rthr, rprm, _ = rainfall._prepare((lon, lat, vmax), dt_s, stat, rain_r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt,
                                                   rain_thresholds, n_groups)
     n_wbin, n_rbin = int(wthr.size), int(rthr.size)
     if (n_wbin + 1) * (n_rbin + 1) > MAX_CELLS:
@@ -100,9 +99,7 @@ def parse_args(argv=None):
     p.add_argument('--rmax-km', type=float, default=None, help='constant radius of maximum wind (default: Willoughby et al. 2006)')
     p.add_argument('--ck-cd', type=float, default=None, help='Ck / Cd of the profile (default: the namelist\'s)')
     analysis.add_track_args(p, 'compound.npz')
-    a = p.parse_args(argv)
-    if not (a.site or a.sites or a.grid):
-        p.error('give sites with --site, --sites or --grid')
+    a = analysis.finish_parse(p, p.parse_args(argv))
     if a.rain_thresholds is None:
         if a.stat != 'total':
             p.error('--stat peak-rate needs --rain-thresholds (mm/h)')
@@ -114,31 +111,26 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    site_lon, site_lat = analysis.collect_sites(args)
-    if site_lon.size == 0:
-        raise SystemExit('no sites')
-    lon, lat, vmax, v, env, groups, gfile, gyear, dt = analysis.load_wind_planes(args.tracks)
-    total_years = len(gfile)
-    res = site_compound(lon, lat, v, vmax, env, groups, site_lon, site_lat, dt, args.wind_thresholds, args.rain_thresholds,
-                        rmax_km=args.rmax_km, ck_cd=args.ck_cd, wind_r_out_km=args.wind_r_out_km, rain_r_out_km=args.rain_r_out_km,
-                        substeps=args.substeps, stat=args.stat, device=args.device, n_groups=total_years)
+    inp = analysis.load_inputs(args, wind=True)
+    site_lon, site_lat, total_years = inp.site_lon, inp.site_lat, inp.total_years
+    res = site_compound(inp.lon, inp.lat, inp.v, inp.vmax, inp.env, inp.groups, site_lon, site_lat, inp.dt_s, args.wind_thresholds,
+                        args.rain_thresholds, rmax_km=args.rmax_km, ck_cd=args.ck_cd, wind_r_out_km=args.wind_r_out_km,
+                        rain_r_out_km=args.rain_r_out_km, substeps=args.substeps, stat=args.stat, device=args.device,
+                        n_groups=total_years)
     counts = res['counts']
     joint = table_return_periods(counts[:, :, 1:, 1:], total_years)
     either = table_return_periods(or_counts(counts), total_years)
-    np.savez(args.out, counts=counts, joint_return_period=joint, either_return_period=either, wind_thresholds=res['wind_thresholds'],
-             rain_thresholds=res['rain_thresholds'], site_lon=site_lon, site_lat=site_lat, total_years=total_years,
-             wind_r_out_km=args.wind_r_out_km, rain_r_out_km=args.rain_r_out_km, substeps=args.substeps, stat=args.stat,
-             rmax_km=np.nan if args.rmax_km is None else args.rmax_km, dt_s=dt, **analysis.group_meta(args.tracks, gfile, gyear))
-    print('%d sites, %d storms, %d groups (%d files), total_years = %d, wind r_out = %g km, rain (%s) r_out = %g km, %d substeps -> %s'
-          % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.wind_r_out_km, args.stat, args.rain_r_out_km,
-             args.substeps, args.out))
+    analysis.save_npz(args, inp, dict(counts=counts, joint_return_period=joint, either_return_period=either,
+                                      wind_thresholds=res['wind_thresholds'], rain_thresholds=res['rain_thresholds'],
+                                      wind_r_out_km=args.wind_r_out_km, rain_r_out_km=args.rain_r_out_km, stat=args.stat),
+                      recorded=('substeps', 'rmax_km'))
+    analysis.print_summary(args, inp, ', wind r_out = %g km, rain (%s) r_out = %g km, %d substeps'
+                           % (args.wind_r_out_km, args.stat, args.rain_r_out_km, args.substeps))
     if site_lon.size <= 10:
         unit = 'mm' if args.stat == 'total' else 'mm/h'
-        print('joint return period (years): rows wind (m/s), columns rain (%s): ' % unit + ' '.join('%6g' % t for t in res['rain_thresholds']))
-        for i in range(site_lon.size):
-            print('  site (%.4f, %.4f)' % (site_lon[i], site_lat[i]))
-            for a, u in enumerate(res['wind_thresholds']):
-                print('    %6g: ' % u + ' '.join('%6.3g' % x for x in joint[i, a]))
+        analysis.print_site_tables('joint return period (years): rows wind (m/s), columns rain (%s): ' % unit
+                                   + ' '.join('%6g' % t for t in res['rain_thresholds']), site_lon, site_lat,
+                                   ['%6g: ' % u for u in res['wind_thresholds']], joint, '%6.3g')
     return 0
 
 

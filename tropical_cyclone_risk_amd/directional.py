@@ -29,7 +29,7 @@ from . import analysis, hazard, windfield
 from . import sitescan
 
 MAX_SECTORS = 8
-MAX_CELLS = 64
+MAX_CELLS = sitescan.MAX_CELLS
 # seven speeds: with the default eight sectors, 8 * (7 + 1) is the 64 cells a call may have
 DEFAULT_THRESHOLDS = np.arange(10, 71, 10).astype(np.float64)
 COMPASS = {1: ['all'], 4: ['N', 'E', 'S', 'W'], 8: ['N', 'NE', 'E', 'SE', 'S', 'SW', 'W', 'NW']}
@@ -54,14 +54,9 @@ def site_directional_wind(lon, lat, v, env, groups, site_lon, site_lat, dt_s, n_
     for: a plane is n_site * n_trk * 8 bytes on the device, which is why they are selectable), in the type and on the device of
     ``lon``.
     """
-    n_sector, sector0_deg, want = _check_sectors(n_sector, sector0_deg, thresholds, return_max)
-    res, fl = _scan(lon, lat, v, env, groups, site_lon, site_lat, dt_s, n_sector, sector0_deg, thresholds, rmax_km, ck_cd, r_out_km,
-                    substeps, want, engine, device, n_groups)
-    planes = res.pop('planes')
-    if return_max is not False and return_max is not None:
-        n_trk = int(lon.shape[0]) if hasattr(lon, 'shape') else len(lon)
-        res['site_dir_max'] = sitescan.stacked_planes(fl, planes, n_sector, int(res['counts'].shape[0]), n_trk)
-    return res
+    scan = _bind(groups, dt_s, n_sector, sector0_deg, thresholds, rmax_km, ck_cd, r_out_km, substeps, n_groups)
+    res, fl = scan((lon, lat, v, env), site_lon, site_lat, return_max, engine, device)
+    return sitescan.attach_planes(res, fl, 'site_dir_max', return_max, lon)
 
 
 def _check_sectors(n_sector, sector0_deg, thresholds, return_max):
@@ -73,26 +68,30 @@ def _check_sectors(n_sector, sector0_deg, thresholds, return_max):
     sector0_deg = float(sector0_deg)
     if not (np.isfinite(sector0_deg) and 0.0 <= sector0_deg < 360.0):
         raise ValueError('sector0_deg must be finite and in [0, 360)')
-    thr = np.asarray(thresholds, dtype=np.float64).reshape(-1)
-    if thr.size < 1 or not np.isfinite(thr).all() or np.any(np.diff(thr) <= 0):
-        raise ValueError('thresholds must be finite and strictly ascending')
+    thr = sitescan.check_ascending(thresholds, sitescan.ASCENDING % 'thresholds')
     if n_sector * (thr.size + 1) > MAX_CELLS:
         raise ValueError('n_sector * (n_bin + 1) must be <= %d' % MAX_CELLS)
     return n_sector, sector0_deg, sitescan.wanted_rows(return_max, n_sector, 'return_max', 'sector')
 
 
-def _scan(lon, lat, v, env, groups, site_lon, site_lat, dt_s, n_sector, sector0_deg, thresholds, rmax_km, ck_cd, r_out_km, substeps,
-          want, engine, device, n_groups):
-    """One call of tcr_directional_*: (dict with ``planes`` = {sector: [n_site][n_trk] plane} for the sectors in want, Flavour)."""
-    planes, fl, thr, prm = windfield._prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
+def _bind(groups, dt_s, n_sector, sector0_deg, thresholds, rmax_km, ck_cd, r_out_km, substeps, n_groups):
+    """site_directional_wind's arguments, checked as far as they stand alone (_check_sectors) and bound into sitescan's
+    scan(tracks = (lon, lat, v, env), site_lon, site_lat, want, engine, device): one call of tcr_directional_*, whose ``planes`` are
+    those of the sectors in want (a return_max).  windfield._prepare needs the tracks: it runs in every call, after want's check."""
+    n_sector, sector0_deg, _ = _check_sectors(n_sector, sector0_deg, thresholds, False)
 
-    def make_args(a, rows):
-        n_bin_, thr_, counts_, _ = a.out
-        return (C.byref(windfield._tracks_struct(a)), C.byref(prm)) + a.sites + (n_sector, sector0_deg, n_bin_, thr_, counts_, rows)
-    res = sitescan.stacked_scan('tcr_directional', planes, fl, groups, n_groups, site_lon, site_lat, thr, n_sector, want, 'dir', engine,
-                                device, make_args)
-    res['sector_from_deg'] = sector_centres(n_sector, sector0_deg)
-    return res, fl
+    def scan(tracks, site_lon, site_lat, want=(), engine=None, device=0):
+        want = sitescan.wanted_rows(want, n_sector, 'return_max', 'sector')
+        planes, fl, thr, prm = windfield._prepare(tracks, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
+
+        def make_args(a, rows):
+            n_bin_, thr_, counts_, _ = a.out
+            return (C.byref(windfield._tracks_struct(a)), C.byref(prm)) + a.sites + (n_sector, sector0_deg, n_bin_, thr_, counts_, rows)
+        res = sitescan.stacked_scan('tcr_directional', planes, fl, groups, n_groups, site_lon, site_lat, thr, n_sector, want, 'dir',
+                                    engine, device, make_args)
+        res['sector_from_deg'] = sector_centres(n_sector, sector0_deg)
+        return res, fl
+    return scan
 
 
 def return_periods(counts, total_years):
@@ -142,12 +141,9 @@ def parse_args(argv=None):
                    help='speeds in m/s; sectors * (thresholds + 1) <= 64 (default: %s)' % ' '.join('%g' % t for t in DEFAULT_THRESHOLDS))
     analysis.add_return_period_arg(p, 'peak wind (m/s) from every sector')
     analysis.add_track_args(p, 'directional.npz')
-    a = p.parse_args(argv)
-    if a.tail_exceedances is not None:
-        p.error('--tail-exceedances is not offered for directional wind: a sector\'s peaks have a point mass at 0 (storms that '
-                'reached the site with no wind from that sector), which a Pareto fit to the excesses does not describe')
-    if not (a.site or a.sites or a.grid):
-        p.error('give sites with --site, --sites or --grid')
+    a = analysis.finish_parse(p, p.parse_args(argv), no_tail='--tail-exceedances is not offered for directional wind: a sector\'s '
+                              'peaks have a point mass at 0 (storms that reached the site with no wind from that sector), which a '
+                              'Pareto fit to the excesses does not describe')
     try:
         _check_sectors(a.sectors, a.sector0_deg, a.thresholds, False)
     except ValueError as e:
@@ -162,45 +158,30 @@ def _sector_name(k, n_sector, centres):
 
 def main(argv=None):
     args = parse_args(argv)
-    site_lon, site_lat = analysis.collect_sites(args)
-    if site_lon.size == 0:
-        raise SystemExit('no sites')
-    lon, lat, _, v, env, groups, gfile, gyear, dt = analysis.load_wind_planes(args.tracks)
-    total_years = len(gfile)
-    kw = dict(rmax_km=args.rmax_km, ck_cd=args.ck_cd, r_out_km=args.r_out_km, substeps=args.substeps, n_groups=total_years)
-    res = site_directional_wind(lon, lat, v, env, groups, site_lon, site_lat, dt, n_sector=args.sectors, sector0_deg=args.sector0_deg,
-                                thresholds=args.thresholds, device=args.device, **kw)
+    inp = analysis.load_inputs(args, wind=True)
+    site_lon, site_lat, total_years = inp.site_lon, inp.site_lat, inp.total_years
+    tracks = (inp.lon, inp.lat, inp.v, tuple(inp.env))
+    scan = _bind(inp.groups, inp.dt_s, args.sectors, args.sector0_deg, args.thresholds, args.rmax_km, args.ck_cd, args.r_out_km,
+                 args.substeps, total_years)
+    res, _ = scan(tracks, site_lon, site_lat, device=args.device)
     more = {}
     if args.return_periods is not None:
-        def one(k, t, x, y):
-            r, _ = _scan(t[0], t[1], t[2], t[3], groups, x, y, dt, args.sectors, float(args.sector0_deg), args.thresholds, kw['rmax_km'],
-                         kw['ck_cd'], kw['r_out_km'], kw['substeps'], [k], None, 0, total_years)
-            r['value'] = r.pop('planes')[k]
-            return r
-        more = sitescan.stacked_return_levels(one, args.sectors, (lon, lat, v, tuple(env)), site_lon, site_lat, total_years,
-                                              args.return_periods, args.device)
+        more = sitescan.stacked_return_levels(scan, args.sectors, tracks, site_lon, site_lat, total_years, args.return_periods,
+                                              args.device)
     rp = return_periods(res['counts'], total_years)
-    centres = res['sector_from_deg']
-    np.savez(args.out, counts=res['counts'], return_period=rp, sector_from_deg=centres, thresholds=res['thresholds'],
-             site_lon=site_lon, site_lat=site_lat, total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps,
-             rmax_km=np.nan if args.rmax_km is None else args.rmax_km, dt_s=dt, **analysis.group_meta(args.tracks, gfile, gyear),
-             **more)
-    print('%d sites, %d storms, %d groups (%d files), total_years = %d, r_out = %g km, %d substeps, %d sectors -> %s'
-          % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.r_out_km, args.substeps, args.sectors,
-             args.out))
+    centres, thr = res['sector_from_deg'], res['thresholds']
+    analysis.save_npz(args, inp, dict(counts=res['counts'], return_period=rp, sector_from_deg=centres, thresholds=thr),
+                      recorded=('r_out_km', 'substeps', 'rmax_km'), more=more)
+    analysis.print_summary(args, inp, ', r_out = %g km, %d substeps, %d sectors' % (args.r_out_km, args.substeps, args.sectors))
     if site_lon.size <= 10:
-        for i, (k, b, period) in enumerate(worst_sector(res['counts'], total_years)):
-            if k < 0:
-                print('  site (%.4f, %.4f): no sector reaches %g m/s' % (site_lon[i], site_lat[i], res['thresholds'][0]))
-            else:
-                print('  site (%.4f, %.4f): worst sector %s: %g m/s every %.3g years'
-                      % (site_lon[i], site_lat[i], _sector_name(k, args.sectors, centres), res['thresholds'][b], period))
-        if more:
-            for k in range(args.sectors):
-                print('peak wind (m/s) from sector %s by return period (years): ' % _sector_name(k, args.sectors, centres)
-                      + ' '.join('%6g' % t for t in more['return_periods']))
-                for i in range(site_lon.size):
-                    print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%6.4g' % h for h in more['return_level'][i, k]))
+        worst = ['no sector reaches %g m/s' % thr[0] if k < 0 else
+                 'worst sector %s: %g m/s every %.3g years' % (_sector_name(k, args.sectors, centres), thr[b], period)
+                 for k, b, period in worst_sector(res['counts'], total_years)]
+        analysis.print_site_rows(None, site_lon, site_lat, worst)
+        for k in range(args.sectors if more else 0):
+            analysis.print_site_rows('peak wind (m/s) from sector %s by return period (years): ' % _sector_name(k, args.sectors, centres)
+                                     + ' '.join('%6g' % t for t in more['return_periods']), site_lon, site_lat,
+                                     more['return_level'][:, k], '%6.4g')
     return 0
 
 

@@ -31,7 +31,7 @@ from . import _lib, analysis, hazard, windfield
 from . import sitescan
 
 MAX_LEVELS = 8
-MAX_CELLS = 64
+MAX_CELLS = sitescan.MAX_CELLS
 DEFAULT_LEVELS = np.array([34.0, 50.0, 64.0]) * 1852.0 / 3600.0          # gale, storm and hurricane force (kt) in m/s
 DEFAULT_HOURS = np.array([1, 3, 6, 12, 24, 48], dtype=np.float64)
 
@@ -53,14 +53,9 @@ def site_duration(lon, lat, v, env, groups, site_lon, site_lat, dt_s, levels=DEF
     [n_level][n_site][n_trk] (hours; NaN: no sample within r_out_km; all NaN for a level not asked for: a plane is
     n_site * n_trk * 8 bytes on the device, which is why they are selectable), in the type and on the device of ``lon``.
     """
-    lev, want = _check_levels(levels, thresholds, return_hours)
-    res, fl = _scan(lon, lat, v, env, groups, site_lon, site_lat, dt_s, lev, thresholds, rmax_km, ck_cd, r_out_km, substeps, want,
-                    engine, device, n_groups)
-    planes = res.pop('planes')
-    if return_hours is not False and return_hours is not None:
-        n_trk = int(lon.shape[0]) if hasattr(lon, 'shape') else len(lon)
-        res['site_hours'] = sitescan.stacked_planes(fl, planes, lev.size, int(res['counts'].shape[0]), n_trk)
-    return res
+    scan = _bind(groups, dt_s, levels, thresholds, rmax_km, ck_cd, r_out_km, substeps, n_groups)
+    res, fl = scan((lon, lat, v, env), site_lon, site_lat, return_hours, engine, device)
+    return sitescan.attach_planes(res, fl, 'site_hours', return_hours, lon)
 
 
 def _check_levels(levels, thresholds, return_hours):
@@ -68,31 +63,34 @@ def _check_levels(levels, thresholds, return_hours):
     lev = np.ascontiguousarray(np.asarray(levels, dtype=np.float64).reshape(-1))
     if not 1 <= lev.size <= MAX_LEVELS:
         raise ValueError('give 1 to %d levels' % MAX_LEVELS)
-    if not np.isfinite(lev).all() or np.any(lev <= 0) or np.any(np.diff(lev) <= 0):
-        raise ValueError('levels must be finite, > 0 and strictly ascending')
-    thr = np.asarray(thresholds, dtype=np.float64).reshape(-1)
-    if thr.size < 1 or not np.isfinite(thr).all() or np.any(thr <= 0) or np.any(np.diff(thr) <= 0):
-        raise ValueError('thresholds must be finite, > 0 and strictly ascending')
+    lev = sitescan.check_ascending(lev, sitescan.ASCENDING_POSITIVE % 'levels', positive=True)
+    thr = sitescan.check_ascending(thresholds, sitescan.ASCENDING_POSITIVE % 'thresholds', positive=True)
     if lev.size * (thr.size + 1) > MAX_CELLS:
         raise ValueError('n_level * (n_bin + 1) must be <= %d' % MAX_CELLS)
     return lev, sitescan.wanted_rows(return_hours, lev.size, 'return_hours', 'level')
 
 
-def _scan(lon, lat, v, env, groups, site_lon, site_lat, dt_s, lev, thresholds, rmax_km, ck_cd, r_out_km, substeps, want, engine, device,
-          n_groups):
-    """One call of tcr_duration_*: (dict with ``planes`` = {level index: [n_site][n_trk] plane} for the levels in want, Flavour)."""
-    planes, fl, thr, prm = windfield._prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
+def _bind(groups, dt_s, levels, thresholds, rmax_km, ck_cd, r_out_km, substeps, n_groups):
+    """site_duration's arguments, checked as far as they stand alone (_check_levels) and bound into sitescan's
+    scan(tracks = (lon, lat, v, env), site_lon, site_lat, want, engine, device): one call of tcr_duration_*, whose ``planes`` are
+    those of the levels in want (a return_hours).  windfield._prepare needs the tracks: it runs in every call, after want's check."""
+    lev, _ = _check_levels(levels, thresholds, False)
     n_level = int(lev.size)
 
-    def make_args(a, hours):
-        n_bin_, thr_, counts_, _ = a.out
-        return (C.byref(windfield._tracks_struct(a)), C.byref(prm)) + a.sites + \
-            (n_level, lev.ctypes.data_as(_lib.DP), n_bin_, thr_, counts_, a.outputs[0], hours)
-    res = sitescan.stacked_scan('tcr_duration', planes, fl, groups, n_groups, site_lon, site_lat, thr, n_level, want, 'hours', engine,
-                                device, make_args, more_outputs=[('half_steps', ('site_group', n_level))])
-    res['hours_per_half_step'] = hours_per_half_step(prm.dt_s, prm.substeps)
-    res['levels'] = lev
-    return res, fl
+    def scan(tracks, site_lon, site_lat, want=(), engine=None, device=0):
+        want = sitescan.wanted_rows(want, n_level, 'return_hours', 'level')
+        planes, fl, thr, prm = windfield._prepare(tracks, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
+
+        def make_args(a, hours):
+            n_bin_, thr_, counts_, _ = a.out
+            return (C.byref(windfield._tracks_struct(a)), C.byref(prm)) + a.sites + \
+                (n_level, lev.ctypes.data_as(_lib.DP), n_bin_, thr_, counts_, a.outputs[0], hours)
+        res = sitescan.stacked_scan('tcr_duration', planes, fl, groups, n_groups, site_lon, site_lat, thr, n_level, want, 'hours',
+                                    engine, device, make_args, more_outputs=[('half_steps', ('site_group', n_level))])
+        res['hours_per_half_step'] = hours_per_half_step(prm.dt_s, prm.substeps)
+        res['levels'] = lev
+        return res, fl
+    return scan
 
 
 # ---------------------------------------------------------------------------------------------------------------- CLI
@@ -116,12 +114,8 @@ def parse_args(argv=None):
                    help='durations in hours (default: %s)' % ' '.join('%g' % t for t in DEFAULT_HOURS))
     analysis.add_return_period_arg(p, 'hours at or above every level')
     analysis.add_track_args(p, 'duration.npz')
-    a = p.parse_args(argv)
-    if a.tail_exceedances is not None:
-        p.error('--tail-exceedances is not offered for durations: they are quantised in half sub-steps, which a Pareto fit to '
-                'the excesses does not describe')
-    if not (a.site or a.sites or a.grid):
-        p.error('give sites with --site, --sites or --grid')
+    a = analysis.finish_parse(p, p.parse_args(argv), no_tail='--tail-exceedances is not offered for durations: they are quantised in '
+                              'half sub-steps, which a Pareto fit to the excesses does not describe')
     try:
         _check_levels(a.levels, a.thresholds, False)
     except ValueError as e:
@@ -131,42 +125,27 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    site_lon, site_lat = analysis.collect_sites(args)
-    if site_lon.size == 0:
-        raise SystemExit('no sites')
-    lon, lat, _, v, env, groups, gfile, gyear, dt = analysis.load_wind_planes(args.tracks)
-    total_years = len(gfile)
-    kw = dict(rmax_km=args.rmax_km, ck_cd=args.ck_cd, r_out_km=args.r_out_km, substeps=args.substeps, n_groups=total_years)
-    res = site_duration(lon, lat, v, env, groups, site_lon, site_lat, dt, levels=args.levels, thresholds=args.thresholds,
-                        device=args.device, **kw)
-    u = res['hours_per_half_step']
-    annual = res['half_steps'].sum(axis=1) * u / total_years
+    inp = analysis.load_inputs(args, wind=True)
+    site_lon, site_lat, total_years = inp.site_lon, inp.site_lat, inp.total_years
+    tracks = (inp.lon, inp.lat, inp.v, tuple(inp.env))
+    scan = _bind(inp.groups, inp.dt_s, args.levels, args.thresholds, args.rmax_km, args.ck_cd, args.r_out_km, args.substeps, total_years)
+    res, _ = scan(tracks, site_lon, site_lat, device=args.device)
+    lev = res['levels']
+    annual = res['half_steps'].sum(axis=1) * res['hours_per_half_step'] / total_years
     more = {}
     if args.return_periods is not None:
-        lev = res['levels']
-
-        def one(l, t, x, y):
-            r, _ = _scan(t[0], t[1], t[2], t[3], groups, x, y, dt, lev, args.thresholds, kw['rmax_km'], kw['ck_cd'], kw['r_out_km'],
-                         kw['substeps'], [l], None, 0, total_years)
-            r['value'] = r.pop('planes')[l]
-            return r
-        more = sitescan.stacked_return_levels(one, lev.size, (lon, lat, v, tuple(env)), site_lon, site_lat, total_years,
-                                              args.return_periods, args.device)
+        more = sitescan.stacked_return_levels(scan, lev.size, tracks, site_lon, site_lat, total_years, args.return_periods, args.device)
     rp = hazard.return_periods(res['counts'], total_years)
-    np.savez(args.out, counts=res['counts'], return_period=rp, annual_hours=annual, levels=res['levels'], thresholds=res['thresholds'],
-             site_lon=site_lon, site_lat=site_lat, total_years=total_years, dt_s=dt, **analysis.group_meta(args.tracks, gfile, gyear),
-             **more)
-    print('%d sites, %d storms, %d groups (%d files), total_years = %d, r_out = %g km, %d substeps -> %s'
-          % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.r_out_km, args.substeps, args.out))
+    analysis.save_npz(args, inp, dict(counts=res['counts'], return_period=rp, annual_hours=annual, levels=lev,
+                                      thresholds=res['thresholds']), more=more)
+    analysis.print_summary(args, inp, ', r_out = %g km, %d substeps' % (args.r_out_km, args.substeps))
     if site_lon.size <= 10:
-        print('hours per year at or above (m/s): ' + ' '.join('%8.4g' % x for x in res['levels']))
-        for i in range(site_lon.size):
-            print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%8.4g' % x for x in annual[i]))
-        if more:
-            for l, x in enumerate(res['levels']):
-                print('hours at or above %.4g m/s by return period (years): ' % x + ' '.join('%6g' % t for t in more['return_periods']))
-                for i in range(site_lon.size):
-                    print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%6.4g' % h for h in more['return_level'][i, l]))
+        analysis.print_site_rows('hours per year at or above (m/s): ' + ' '.join('%8.4g' % x for x in lev), site_lon, site_lat,
+                                 annual, '%8.4g')
+        for l, x in enumerate(lev if more else ()):
+            analysis.print_site_rows('hours at or above %.4g m/s by return period (years): ' % x
+                                     + ' '.join('%6g' % t for t in more['return_periods']), site_lon, site_lat,
+                                     more['return_level'][:, l], '%6.4g')
     return 0
 
 

@@ -257,9 +257,9 @@ def print_top_events(table, site_lon, site_lat, storm_year=None, unit='m/s', n_t
     if site_lon.size > 10:
         return
     ptr, storm, value = (analysis.to_numpy(table[k]) for k in ('site_ptr', 'storm', 'value'))
-    print('largest events (%s) by site: storm index (year) value' % unit)
+    rows = []
     for i in range(site_lon.size):
         s, v = storm[ptr[i]:ptr[i + 1]], value[ptr[i]:ptr[i + 1]]
         top = np.argsort(-v, kind='stable')[:n_top]
-        text = ' '.join('%d (%s) %.4g' % (s[t], '-' if storm_year is None else '%d' % storm_year[s[t]], v[t]) for t in top)
-        print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + (text or 'none'))
+        rows.append(' '.join('%d (%s) %.4g' % (s[t], '-' if storm_year is None else '%d' % storm_year[s[t]], v[t]) for t in top) or 'none')
+    analysis.print_site_rows('largest events (%s) by site: storm index (year) value' % unit, site_lon, site_lat, rows)

@@ -84,44 +84,17 @@ def parse_args(argv=None):
     analysis.add_return_period_arg(p, 'near-site intensity (m/s)')
     analysis.add_events_arg(p, 'near-site intensity (m/s)')
     analysis.add_track_args(p, 'hazard.npz')
-    a = p.parse_args(argv)
-    analysis.check_return_period_args(p, a)
-    analysis.check_events_args(p, a)
-    if not (a.site or a.sites or a.grid):
-        p.error('give sites with --site, --sites or --grid')
-    return a
+    return analysis.finish_parse(p, p.parse_args(argv))
 
 
 def main(argv=None):
     args = parse_args(argv)
-    site_lon, site_lat = collect_sites(args)
-    if site_lon.size == 0:
-        raise SystemExit('no sites')
-    lon, lat, vmax, groups, gfile, gyear = load_groups(args.tracks)
-    total_years = len(gfile)
-    kw = dict(radius_km=args.radius_km, thresholds=args.thresholds, n_groups=total_years)
-    more = {}
-    if args.return_periods is None:
-        res = site_hazard(lon, lat, vmax, groups, site_lon, site_lat, device=args.device, **kw)
-    else:
-        from . import levels
-        res = levels.device_levels(lambda t, x, y: site_hazard(t[0], t[1], t[2], groups, x, y, return_max=True, **kw),
-                                   (lon, lat, vmax), site_lon, site_lat, total_years, args.return_periods, 'site_max', args.device,
-                                   tail_exceedances=args.tail_exceedances)
-        more = levels.npz_keys(res)
-    rp = return_periods(res['counts'], total_years)
-    np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,
-             total_years=total_years, radius_km=args.radius_km, **analysis.group_meta(args.tracks, gfile, gyear), **more)
-    print('%d sites, %d storms, %d groups (%d files), total_years = %d -> %s'
-          % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.out))
-    analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp)
-    if more:
-        levels.print_return_levels(res, site_lon, site_lat)
-    if args.events_out is not None:
-        from . import events
-        events.write_cli_events(args, lambda t, x, y: site_hazard(t[0], t[1], t[2], groups, x, y, return_max=True, **kw),
-                                (lon, lat, vmax), site_lon, site_lat, 'site_max', 'm/s', groups, gfile, gyear)
-    return 0
+    inp = analysis.load_inputs(args, spacing=False)
+    kw = dict(radius_km=args.radius_km, thresholds=args.thresholds, n_groups=inp.total_years)
+
+    def block(t, x, y, plane=False, device=0):
+        return site_hazard(t[0], t[1], t[2], inp.groups, x, y, return_max=plane, device=device, **kw)
+    return analysis.threshold_main(args, inp, block, (inp.lon, inp.lat, inp.vmax), 'site_max', arrays=dict(radius_km=args.radius_km))
 
 
 if __name__ == '__main__':

@@ -265,15 +265,15 @@ def print_return_levels(res, site_lon, site_lat, unit='m/s'):
     """The return-level table of up to 10 sites (more: nothing), as analysis.print_return_periods."""
     if site_lon.size > 10:
         return
-    print('return level (%s) by return period (years): ' % unit + ' '.join('%6g' % t for t in res['return_periods']))
-    for i in range(site_lon.size):
-        print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%6.4g' % v for v in res['return_level'][i]))
+    periods = ' '.join('%6g' % t for t in res['return_periods'])
+    analysis.print_site_rows('return level (%s) by return period (years): ' % unit + periods, site_lon, site_lat, res['return_level'],
+                             '%6.4g')
     if 'tail_level' not in res:
         return
-    print('fitted tail level (%s) by return period (years): ' % unit + ' '.join('%6g' % t for t in res['return_periods']))
-    for i in range(site_lon.size):
-        print('  site (%.4f, %.4f): ' % (site_lon[i], site_lat[i]) + ' '.join('%6.4g' % v for v in res['tail_level'][i])
-              + '   (xi %.3g, sigma %.4g, threshold %.4g)' % (res['tail_xi'][i], res['tail_sigma'][i], res['tail_threshold'][i]))
+    rows = [' '.join('%6.4g' % v for v in res['tail_level'][i])
+            + '   (xi %.3g, sigma %.4g, threshold %.4g)' % (res['tail_xi'][i], res['tail_sigma'][i], res['tail_threshold'][i])
+            for i in range(site_lon.size)]
+    analysis.print_site_rows('fitted tail level (%s) by return period (years): ' % unit + periods, site_lon, site_lat, rows)
 
 
 def npz_keys(res):

@@ -57,7 +57,7 @@ def portfolio_loss(lon, lat, v, env, groups, site_lon, site_lat, value, dt_s, v_
     caller's site order, ``thresholds``; arrays in the type and on the device of ``lon``.  No sum uses atomics: a repeated call
     gives the same bits.
     """
-    planes, fl, thr, wprm = windfield._prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
+    planes, fl, thr, wprm = windfield._prepare((lon, lat, v, env), dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
     xp, conv = fl.xp, fl.conv
     v_thresh = float(v_thresh)
     if not (np.isfinite(v_thresh) and v_thresh >= 0):
@@ -164,23 +164,20 @@ def main(argv=None):
     site_lon, site_lat, value, vh, any_vh = read_exposure_csv(args.exposure, args.v_half)
     if site_lon.size == 0:
         raise SystemExit('no exposure')
-    lon, lat, _, v, env, groups, gfile, gyear, dt = analysis.load_wind_planes(args.tracks)
-    total_years = len(gfile)
-    res = portfolio_loss(lon, lat, v, env, groups, site_lon, site_lat, value, dt, v_thresh=args.v_thresh,
+    inp = analysis.load_inputs(args, wind=True, sites=(site_lon, site_lat))
+    total_years = inp.total_years
+    res = portfolio_loss(inp.lon, inp.lat, inp.v, inp.env, inp.groups, site_lon, site_lat, value, inp.dt_s, v_thresh=args.v_thresh,
                          v_half=vh if any_vh else args.v_half, rmax_km=args.rmax_km, ck_cd=args.ck_cd, r_out_km=args.r_out_km,
                          substeps=args.substeps, device=args.device, n_groups=total_years)
     T = args.return_periods
     aal = average_annual_loss(res['year_agg'], total_years)
     aep, oep = loss_curve(res['year_agg'], total_years, T), loss_curve(res['year_max'], total_years, T)
-    np.savez(args.out, event_loss=res['event_loss'], year_agg=res['year_agg'], year_max=res['year_max'], site_loss=res['site_loss'],
-             loss_cost=res['site_loss'] / total_years, counts=res['counts'], thresholds=res['thresholds'], aal=aal,
-             return_periods=T, aep=aep, oep=oep, site_lon=site_lon, site_lat=site_lat, value=value, v_half=vh,
-             v_thresh=args.v_thresh, total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps,
-             rmax_km=np.nan if args.rmax_km is None else args.rmax_km, dt_s=dt,
-             **analysis.group_meta(args.tracks, gfile, gyear))
-    print('%d sites (total value %g), %d storms, %d groups (%d files), total_years = %d, r_out = %g km, %d substeps -> %s'
-          % (site_lon.size, value.sum(), lon.shape[0], total_years, len(args.tracks), total_years, args.r_out_km, args.substeps,
-             args.out))
+    analysis.save_npz(args, inp, dict(event_loss=res['event_loss'], year_agg=res['year_agg'], year_max=res['year_max'],
+                                      site_loss=res['site_loss'], loss_cost=res['site_loss'] / total_years, counts=res['counts'],
+                                      thresholds=res['thresholds'], aal=aal, return_periods=T, aep=aep, oep=oep, value=value, v_half=vh,
+                                      v_thresh=args.v_thresh), recorded=('r_out_km', 'substeps', 'rmax_km'))
+    analysis.print_summary(args, inp, ', r_out = %g km, %d substeps' % (args.r_out_km, args.substeps),
+                           site_note=' (total value %g)' % value.sum())
     print('average annual loss: %.6g' % aal)
     print('return period (years):      ' + ' '.join('%10g' % t for t in T))
     print('aggregate loss (AEP):       ' + ' '.join('%10.4g' % x for x in aep))

@@ -25,11 +25,9 @@ import sys
 
 import numpy as np
 
-from . import _lib, analysis, hazard
-from .sitescan import site_scan
+from . import _lib, analysis, sitescan
+from .sitescan import MAX_R_OUT_KM, MAX_SUBSTEPS, site_scan  # noqa: F401
 
-MAX_SUBSTEPS = 64
-MAX_R_OUT_KM = 2000.0
 DEFAULT_RAIN_THRESHOLDS = np.array([25, 50, 75, 100, 150, 200, 250, 300, 400, 500], dtype=np.float64)      # mm
 # R-CLIPER, the TRMM fit: T0, Tm (inches/day), rm, re (km) = a + b U
 DEFAULT_COEFFICIENTS = ((-1.10, -1.60, 64.5, 150.0), (3.96, 4.80, -13.0, -16.0))
@@ -51,7 +49,7 @@ def site_rain(lon, lat, vmax, groups, site_lon, site_lat, dt_s, stat='total', r_
     ``thresholds``, and with ``return_values`` ``site_total`` or ``site_peak_rate`` [n_site][n_trk] (NaN: no sample within
     r_out_km), in the type and on the device of ``lon``.
     """
-    planes, fl, thr, prm, key = _prepare(lon, lat, vmax, dt_s, stat, r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt, thresholds,
+    planes, fl, thr, prm, key = _prepare((lon, lat, vmax), dt_s, stat, r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt, thresholds,
                                          n_groups)
 
     def make_args(a):
@@ -63,27 +61,20 @@ def site_rain(lon, lat, vmax, groups, site_lon, site_lat, dt_s, stat='total', r_
     return res
 
 
-def _prepare(lon, lat, vmax, dt_s, stat, r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt, thresholds, n_groups):
+def _prepare(tracks, dt_s, stat, r_out_km, substeps, coefficients, v_lo_kt, v_hi_kt, thresholds, n_groups):
     """The argument checks (ValueError, before the library is touched): (planes, their analysis.Flavour, thresholds,
-    tcr_rain_params, the name of the per-storm output)."""
-    planes, fl = analysis.as_planes((lon, lat, vmax), 'lon, lat and vmax')
+    tcr_rain_params, the name of the per-storm output).  tracks: (lon, lat, vmax)."""
+    planes, fl = analysis.as_planes(tuple(tracks), 'lon, lat and vmax')
     if int(planes[0].shape[1]) < 1:
         raise ValueError('the tracks need at least one sample')
     if stat not in STATS:
         raise ValueError("stat must be 'total' or 'peak-rate'")
-    dt_s = float(dt_s)
-    if not (np.isfinite(dt_s) and dt_s > 0):
-        raise ValueError('dt_s must be finite and > 0')
-    r_out_km = float(r_out_km)
-    if not 0.0 < r_out_km <= MAX_R_OUT_KM:
-        raise ValueError('r_out_km must be in (0, %g]' % MAX_R_OUT_KM)
-    if isinstance(substeps, bool) or int(substeps) != substeps or not 1 <= int(substeps) <= MAX_SUBSTEPS:
-        raise ValueError('substeps must be an integer in [1, %d]' % MAX_SUBSTEPS)
-    if stat == 'peak-rate' and thresholds is DEFAULT_RAIN_THRESHOLDS:
+    dt_s = sitescan.check_dt(dt_s)
+    r_out_km = sitescan.check_r_out(r_out_km)
+    substeps = sitescan.check_substeps(substeps)
+    if stat == 'peak-rate' and thresholds is DEFAULT_RAIN_THRESHOLDS:       # (by identity: the caller's object, unconverted)
         raise ValueError("stat='peak-rate' needs explicit thresholds (mm/h): the defaults are storm totals in mm")
-    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
-    if not 1 <= thr.size <= 64 or not np.isfinite(thr).all() or np.any(np.diff(thr) <= 0):
-        raise ValueError('thresholds must be 1 to 64 finite, strictly ascending values')
+    thr = sitescan.check_ascending(thresholds, sitescan.BOUNDED_THRESHOLDS, max_size=sitescan.MAX_CELLS)
     try:
         a, b = (np.asarray(c, dtype=np.float64).reshape(-1) for c in (DEFAULT_COEFFICIENTS if coefficients is None else coefficients))
     except (TypeError, ValueError):
@@ -97,11 +88,10 @@ def _prepare(lon, lat, vmax, dt_s, stat, r_out_km, substeps, coefficients, v_lo_
         u = 1.0 + (kt - 35.0) / 33.0
         if not (a[2] + b[2] * u > 0 and a[3] + b[3] * u > 0 and a[1] + b[1] * u >= 0):
             raise ValueError('the coefficients must give rm > 0, re > 0 and Tm >= 0 at v_lo_kt and at v_hi_kt')
-    if n_groups is not None and int(n_groups) < 1:
-        raise ValueError('n_groups must be >= 1')
+    sitescan.check_n_groups(n_groups)
     code, key = STATS[stat]
     prm = _lib.RainParams(dt_s=dt_s, r_out_km=r_out_km, v_lo_kt=v_lo_kt, v_hi_kt=v_hi_kt, a=(C.c_double * 4)(*a),
-                          b=(C.c_double * 4)(*b), substeps=int(substeps), stat=code)
+                          b=(C.c_double * 4)(*b), substeps=substeps, stat=code)
     return planes, fl, thr, prm, key
 
 
@@ -119,11 +109,7 @@ def parse_args(argv=None):
     analysis.add_return_period_arg(p, 'storm-total rain (mm) or peak rain rate (mm/h)')
     analysis.add_events_arg(p, 'storm-total rain (mm) or peak rain rate (mm/h)')
     analysis.add_track_args(p, 'rain.npz')
-    a = p.parse_args(argv)
-    analysis.check_return_period_args(p, a)
-    analysis.check_events_args(p, a)
-    if not (a.site or a.sites or a.grid):
-        p.error('give sites with --site, --sites or --grid')
+    a = analysis.finish_parse(p, p.parse_args(argv))
     if a.thresholds is None:
         if a.stat != 'total':
             p.error('--stat peak-rate needs --thresholds (mm/h)')
@@ -133,37 +119,15 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    site_lon, site_lat = analysis.collect_sites(args)
-    if site_lon.size == 0:
-        raise SystemExit('no sites')
-    lon, lat, vmax, groups, gfile, gyear, more = analysis.load_groups(args.tracks, extra=('time',))
-    dt = analysis.sample_spacing(more['time'])
-    total_years = len(gfile)
-    kw = dict(stat=args.stat, r_out_km=args.r_out_km, substeps=args.substeps, thresholds=args.thresholds, n_groups=total_years)
-    more = {}
-    if args.return_periods is None:
-        res = site_rain(lon, lat, vmax, groups, site_lon, site_lat, dt, device=args.device, **kw)
-    else:
-        from . import levels
-        res = levels.device_levels(lambda t, x, y: site_rain(t[0], t[1], t[2], groups, x, y, dt, return_values=True, **kw),
-                                   (lon, lat, vmax), site_lon, site_lat, total_years, args.return_periods, STATS[args.stat][1],
-                                   args.device, tail_exceedances=args.tail_exceedances)
-        more = levels.npz_keys(res)
-    rp = hazard.return_periods(res['counts'], total_years)
-    np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,
-             total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps, stat=args.stat, dt_s=dt,
-             **analysis.group_meta(args.tracks, gfile, gyear), **more)
-    print('%d sites, %d storms, %d groups (%d files), total_years = %d, %s, r_out = %g km, %d substeps -> %s'
-          % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.stat, args.r_out_km, args.substeps, args.out))
-    unit = 'mm' if args.stat == 'total' else 'mm/h'
-    analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp, unit=unit)
-    if more:
-        levels.print_return_levels(res, site_lon, site_lat, unit=unit)
-    if args.events_out is not None:
-        from . import events
-        events.write_cli_events(args, lambda t, x, y: site_rain(t[0], t[1], t[2], groups, x, y, dt, return_values=True, **kw),
-                                (lon, lat, vmax), site_lon, site_lat, STATS[args.stat][1], unit, groups, gfile, gyear)
-    return 0
+    inp = analysis.load_inputs(args)
+    kw = dict(stat=args.stat, r_out_km=args.r_out_km, substeps=args.substeps, thresholds=args.thresholds, n_groups=inp.total_years)
+
+    def block(t, x, y, plane=False, device=0):
+        return site_rain(t[0], t[1], t[2], inp.groups, x, y, inp.dt_s, return_values=plane, device=device, **kw)
+    return analysis.threshold_main(args, inp, block, (inp.lon, inp.lat, inp.vmax), STATS[args.stat][1],
+                                   unit='mm' if args.stat == 'total' else 'mm/h', arrays=dict(stat=args.stat),
+                                   recorded=('r_out_km', 'substeps'),
+                                   middle=', %s, r_out = %g km, %d substeps' % (args.stat, args.r_out_km, args.substeps))
 
 
 if __name__ == '__main__':

@@ -5,9 +5,15 @@ accumulation windows and directional wind.  ``site_scan`` checks the sites and g
 (the storms of a group next to each other, the sites in Z-order), makes the call and maps every output back to the caller's site
 and storm order.
 
+The argument checks the analyses have in common live here, one function each (``check_dt``, ``check_r_out``,
+``check_substeps``, ``check_n_groups``, ``check_ascending``), with the limits they test; none touches the library.
+
 The last three analyses count several values per storm, one per row (a wind level, a window length, a compass sector), each with
-an optional [n_site][n_trk] plane.  ``wanted_rows``, ``stacked_scan``, ``stacked_planes`` and ``stacked_return_levels`` are what
-they share."""
+an optional [n_site][n_trk] plane.  Each binds its arguments once (its ``_bind``) into a ``scan(tracks, site_lon, site_lat, want=(),
+engine=None, device=0)`` -> (dict with ``planes`` = {row: plane} for the rows in want, Flavour), which its public function, its
+command line and ``stacked_return_levels`` call, any number of times: every call makes its own parameter struct and keeps it, the
+thresholds and the row arrays alive until the library returns.  ``wanted_rows``, ``stacked_scan``, ``stacked_planes``,
+``attach_planes`` and ``stacked_return_levels`` are what they share."""
 import collections
 import ctypes as C
 
@@ -22,6 +28,57 @@ from .analysis import group_index
 # ``outputs``, those of the extra outputs (both empty when the analysis names none).
 ScanArgs = collections.namedtuple('ScanArgs', 'tracks planes sites out extras outputs')
 
+MAX_SUBSTEPS = 64
+MAX_R_OUT_KM = 2000.0
+MAX_CELLS = 64          # the cells of the scan's histogram per (site, group) (kHzMaxBin), and so the most thresholds of a call
+BAD_DT = 'dt_s must be finite and > 0'
+# the three wordings of check_ascending's message: % the noun, and for the footprints' thresholds in full
+ASCENDING = '%s must be finite and strictly ascending'
+ASCENDING_POSITIVE = '%s must be finite, > 0 and strictly ascending'
+BOUNDED_THRESHOLDS = 'thresholds must be 1 to %d finite, strictly ascending values' % MAX_CELLS
+
+
+# ------------------------------------------------------------------------------------------------------- shared checks
+def check_dt(dt_s):
+    """The sample spacing (s) as a float: finite and > 0."""
+    dt_s = float(dt_s)
+    if not (np.isfinite(dt_s) and dt_s > 0):
+        raise ValueError(BAD_DT)
+    return dt_s
+
+
+def check_r_out(r_out_km):
+    """The outer radius (km) as a float, in (0, MAX_R_OUT_KM]."""
+    r_out_km = float(r_out_km)
+    if not 0.0 < r_out_km <= MAX_R_OUT_KM:
+        raise ValueError('r_out_km must be in (0, %g]' % MAX_R_OUT_KM)
+    return r_out_km
+
+
+def check_substeps(substeps):
+    """The evaluation points per sample interval as an int, in [1, MAX_SUBSTEPS]; a bool is not an integer here."""
+    if isinstance(substeps, bool) or int(substeps) != substeps or not 1 <= int(substeps) <= MAX_SUBSTEPS:
+        raise ValueError('substeps must be an integer in [1, %d]' % MAX_SUBSTEPS)
+    return int(substeps)
+
+
+def check_n_groups(n_groups):
+    """None (site_scan takes max + 1), or >= 1."""
+    if n_groups is not None and int(n_groups) < 1:
+        raise ValueError('n_groups must be >= 1')
+
+
+def check_ascending(values, message, positive=False, max_size=None):
+    """values as a contiguous fp64 vector: at least one (at most max_size), finite, strictly ascending and with positive > 0.
+    message: the ValueError's text, one of the wordings above with its noun."""
+    a = np.ascontiguousarray(np.asarray(values, dtype=np.float64).reshape(-1))
+    if a.size < 1 or (max_size is not None and a.size > max_size) or not np.isfinite(a).all() or (positive and np.any(a <= 0)) \
+            or np.any(np.diff(a) <= 0):
+        raise ValueError(message)
+    return a
+
+
+# ------------------------------------------------------------------------------------------------------------ the scan
 
 def spatial_order(lon, lat, xp):
     """Z-order (Morton) of the sites on a 2^16 x 2^16 lon / lat raster: runs of consecutive sites are compact patches, which
@@ -169,12 +226,27 @@ def stacked_planes(fl, planes, n_row, n_site, n_trk):
     return out
 
 
-def stacked_return_levels(scan_row, n_row, planes, site_lon, site_lat, total_years, return_periods, device):
+def attach_planes(res, fl, key, asked, lon):
+    """The end of a stacked analysis's public function: a bound scan's ``planes`` leave its dict, and come back under key as
+    stacked_planes' [n_row][n_site][n_trk] when the caller asked for any (asked: its return_* argument; lon: its first plane)."""
+    planes = res.pop('planes')
+    if asked is not False and asked is not None:
+        n_trk = int(lon.shape[0]) if hasattr(lon, 'shape') else len(lon)
+        res[key] = stacked_planes(fl, planes, int(res['counts'].shape[2]), int(res['counts'].shape[0]), n_trk)
+    return res
+
+
+def stacked_return_levels(scan, n_row, tracks, site_lon, site_lat, total_years, return_periods, device):
     """What --return-periods adds to the .npz of a stacked analysis: one blocked levels.device_levels pass per row, each with
-    that row's plane only, and ``return_level`` stacked to [n_site][n_row][T].  scan_row(i, planes, lon_block, lat_block): the
-    analysis's scan with row i's plane under 'value'."""
+    that row's plane only, and ``return_level`` stacked to [n_site][n_row][T].  scan: the analysis's bound scan, called once per
+    row and site block with want = [row]; tracks: its track planes (NumPy), which go to the device once per row."""
     from . import levels
-    per_row = [levels.device_levels(lambda t, x, y, i=i: scan_row(i, t, x, y), planes, site_lon, site_lat, total_years,
+
+    def row_scan(i, t, x, y):
+        r, _ = scan(t, x, y, want=[i])
+        r['value'] = r.pop('planes')[i]
+        return r
+    per_row = [levels.device_levels(lambda t, x, y, i=i: row_scan(i, t, x, y), tracks, site_lon, site_lat, total_years,
                                     return_periods, 'value', device) for i in range(n_row)]
     return dict(return_level=np.stack([r['return_level'] for r in per_row], axis=1), return_periods=per_row[0]['return_periods'],
                 n_reach=per_row[0]['n_reach'])

@@ -25,12 +25,9 @@ import sys
 
 import numpy as np
 
-from . import _lib, analysis, hazard
+from . import _lib, analysis, sitescan
 from .analysis import DEFAULT_THRESHOLDS, ENV_VARS  # noqa: F401
-from .sitescan import site_scan
-
-MAX_SUBSTEPS = 64
-MAX_R_OUT_KM = 2000.0
+from .sitescan import MAX_R_OUT_KM, MAX_SUBSTEPS, site_scan  # noqa: F401
 
 
 def _default_ck_cd():
@@ -64,7 +61,7 @@ def site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt_s, rmax_km=None, 
     ``thresholds``, and with ``return_max`` ``site_max`` [n_site][n_trk] (m/s; NaN: no sample within r_out_km), in the type and
     on the device of ``lon``.
     """
-    planes, fl, thr, prm = _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
+    planes, fl, thr, prm = _prepare((lon, lat, v, env), dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups)
 
     def make_args(a):
         return (C.byref(_tracks_struct(a)), C.byref(prm)) + a.sites + a.out
@@ -77,9 +74,10 @@ def _tracks_struct(a):
     return _lib.WindTracks(lon=p[0], lat=p[1], v=p[2], u250=p[3], v250=p[4], u850=p[5], v850=p[6], rmax_km=p[7], **a.tracks)
 
 
-def _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups):
+def _prepare(tracks, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresholds, n_groups):
     """The footprint's argument checks (ValueError, before the library is touched): (planes, their analysis.Flavour, thresholds,
-    tcr_wind_params), shared with loss.portfolio_loss."""
+    tcr_wind_params), shared with the analyses built on the footprint.  tracks: (lon, lat, v, env)."""
+    lon, lat, v, env = tracks
     if len(env) != 4:
         raise ValueError('env must be (u250, v250, u850, v850)')
     planes, fl = analysis.as_planes((lon, lat, v) + tuple(env), 'lon, lat, v and the four env planes')
@@ -87,21 +85,13 @@ def _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresho
     n_trk, n_t = int(planes[0].shape[0]), int(planes[0].shape[1])
     if n_t < 1:
         raise ValueError('the tracks need at least one sample')
-    dt_s = float(dt_s)
-    if not (np.isfinite(dt_s) and dt_s > 0):
-        raise ValueError('dt_s must be finite and > 0')
+    dt_s = sitescan.check_dt(dt_s)
     ck_cd = _default_ck_cd() if ck_cd is None else float(ck_cd)
     if not 0.0 < ck_cd < 2.0:
         raise ValueError('ck_cd must be in (0, 2)')
-    r_out_km = float(r_out_km)
-    if not 0.0 < r_out_km <= MAX_R_OUT_KM:
-        raise ValueError('r_out_km must be in (0, %g]' % MAX_R_OUT_KM)
-    if isinstance(substeps, bool) or int(substeps) != substeps or not 1 <= int(substeps) <= MAX_SUBSTEPS:
-        raise ValueError('substeps must be an integer in [1, %d]' % MAX_SUBSTEPS)
-    substeps = int(substeps)
-    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
-    if not 1 <= thr.size <= 64 or not np.isfinite(thr).all() or np.any(np.diff(thr) <= 0):
-        raise ValueError('thresholds must be 1 to 64 finite, strictly ascending values')
+    r_out_km = sitescan.check_r_out(r_out_km)
+    substeps = sitescan.check_substeps(substeps)
+    thr = sitescan.check_ascending(thresholds, sitescan.BOUNDED_THRESHOLDS, max_size=sitescan.MAX_CELLS)
     rm_const = 0.0
     if rmax_km is not None:
         if np.ndim(analysis.to_numpy(rmax_km)) == 0:
@@ -119,8 +109,7 @@ def _prepare(lon, lat, v, env, dt_s, rmax_km, ck_cd, r_out_km, substeps, thresho
             if bool((used & ~ok).any()):
                 raise ValueError('rmax_km must be finite and > 0 at every sample of a track')
             planes.append(rm_plane)
-    if n_groups is not None and int(n_groups) < 1:
-        raise ValueError('n_groups must be >= 1')
+    sitescan.check_n_groups(n_groups)
     return planes, fl, thr, _lib.WindParams(dt_s=dt_s, ck_cd=ck_cd, r_out_km=r_out_km, rmax_const_km=rm_const, substeps=substeps)
 
 
@@ -134,47 +123,20 @@ def parse_args(argv=None):
     analysis.add_return_period_arg(p, 'peak wind (m/s)')
     analysis.add_events_arg(p, 'peak wind (m/s)')
     analysis.add_track_args(p, 'wind.npz')
-    a = p.parse_args(argv)
-    analysis.check_return_period_args(p, a)
-    analysis.check_events_args(p, a)
-    if not (a.site or a.sites or a.grid):
-        p.error('give sites with --site, --sites or --grid')
-    return a
+    return analysis.finish_parse(p, p.parse_args(argv))
 
 
 def main(argv=None):
     args = parse_args(argv)
-    site_lon, site_lat = analysis.collect_sites(args)
-    if site_lon.size == 0:
-        raise SystemExit('no sites')
-    lon, lat, _, v, env, groups, gfile, gyear, dt = analysis.load_wind_planes(args.tracks)
-    total_years = len(gfile)
+    inp = analysis.load_inputs(args, wind=True)
     kw = dict(rmax_km=args.rmax_km, ck_cd=args.ck_cd, r_out_km=args.r_out_km, substeps=args.substeps, thresholds=args.thresholds,
-              n_groups=total_years)
-    more = {}
-    if args.return_periods is None:
-        res = site_wind(lon, lat, v, env, groups, site_lon, site_lat, dt, device=args.device, **kw)
-    else:
-        from . import levels
-        res = levels.device_levels(lambda t, x, y: site_wind(t[0], t[1], t[2], t[3], groups, x, y, dt, return_max=True, **kw),
-                                   (lon, lat, v, tuple(env)), site_lon, site_lat, total_years, args.return_periods, 'site_max', args.device,
-                                   tail_exceedances=args.tail_exceedances)
-        more = levels.npz_keys(res)
-    rp = hazard.return_periods(res['counts'], total_years)
-    np.savez(args.out, counts=res['counts'], return_period=rp, thresholds=res['thresholds'], site_lon=site_lon, site_lat=site_lat,
-             total_years=total_years, r_out_km=args.r_out_km, substeps=args.substeps,
-             rmax_km=np.nan if args.rmax_km is None else args.rmax_km, dt_s=dt,
-             **analysis.group_meta(args.tracks, gfile, gyear), **more)
-    print('%d sites, %d storms, %d groups (%d files), total_years = %d, r_out = %g km, %d substeps -> %s'
-          % (site_lon.size, lon.shape[0], total_years, len(args.tracks), total_years, args.r_out_km, args.substeps, args.out))
-    analysis.print_return_periods(res['thresholds'], site_lon, site_lat, rp)
-    if more:
-        levels.print_return_levels(res, site_lon, site_lat)
-    if args.events_out is not None:
-        from . import events
-        events.write_cli_events(args, lambda t, x, y: site_wind(t[0], t[1], t[2], t[3], groups, x, y, dt, return_max=True, **kw),
-                                (lon, lat, v, tuple(env)), site_lon, site_lat, 'site_max', 'm/s', groups, gfile, gyear)
-    return 0
+              n_groups=inp.total_years)
+
+    def block(t, x, y, plane=False, device=0):
+        return site_wind(t[0], t[1], t[2], t[3], inp.groups, x, y, inp.dt_s, return_max=plane, device=device, **kw)
+    return analysis.threshold_main(args, inp, block, (inp.lon, inp.lat, inp.v, tuple(inp.env)), 'site_max',
+                                   recorded=('r_out_km', 'substeps', 'rmax_km'),
+                                   middle=', r_out = %g km, %d substeps' % (args.r_out_km, args.substeps))
 
 
 if __name__ == '__main__':
