@@ -923,6 +923,68 @@ int tcr_accumulation_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const t
 /* (site, record) pairs the last tcr_accumulation_* call of this context evaluated after culling; waits for that call */
 int tcr_accumulation_pairs(tcr_ctx *ctx, int64_t *pairs);
 
+/* ---- closest approach: passage distance, time, intensity, motion and side at sites -------------------------------------- */
+/* replaces: nothing in the reference's code; the "how did it pass" next to the other analyses' "how strong".  Every other per-site
+ * analysis reduces a storm to one extreme at a site; this one keeps the geometry of the passage: the frequency of passages by
+ * distance band and intensity (the statistic behind "hurricanes passing within 50 nmi", the joint-probability method of coastal
+ * surge work, siting studies) and the per-storm parameters at the closest point of approach (CPA).
+ *   tracks          tcr_hazard_tracks (lon, lat, vmax, groups).  A storm's track is the samples before the first with a non-finite
+ *                   lon, lat or vmax; a track of fewer than 2 samples has no records.
+ *   rm              rmax_km: an optional [n_trk][row_stride] plane (km); prm->rmax_const_km > 0: that value everywhere; both NULL /
+ *                   0 (tcr_windfield_*'s rules): Willoughby et al. (2006), 46.4 exp(-0.0155 v + 0.0169 |lat|) km at every sample.
+ *                   A track with an rm that is not finite and > 0 at one of its samples has no records.
+ *   records         (n - 1) substeps + 1 per storm of n samples: the samples, and substeps - 1 sub-samples between neighbours, as
+ *                   the wind footprint's: dl = lon_k+1 - lon_k, dl -= 360 floor((dl + 180) / 360) (the short way round), and lon,
+ *                   lat, v and rm linear in tau = j / substeps.
+ *   motion          of a record: that of the segment [k, k + 1] it lies on; the track's last record takes the last segment's.
+ *                   With dl wrapped as above, phim = (lat_k + lat_k+1) / 2 and Re = 6.3781e6 m:
+ *                   ue = Re cos(phim) rad(dl) / dt_s, un = Re rad(lat_k+1 - lat_k) / dt_s, speed = sqrt(ue^2 + un^2),
+ *                   heading = atan2(ue, un) in degrees, mapped to [0, 360); NaN when ue == un == 0.
+ *   CPA             per (site, storm), over the records with haversine argument q = sin^2(dphi / 2) + cos phi1 cos phi2
+ *                   sin^2(dlam / 2) <= a_R = sin^2(band_km[n_band - 1] / (2 Re / 1000)): the record of least q; on equal q the
+ *                   earliest.  Taken on the records: the minimum along the chord between two records is not modelled, substeps
+ *                   is the refinement.
+ *   planes          a host array of 7 device pointers (host pointers in tcr_approach_host); the array may be NULL, and so may any
+ *                   entry (not written).  Entry k is a [n_site][n_trk] plane of the CPA record's (NaN in every plane when the storm
+ *                   has no included record):
+ *                     0 distance_km  (Re / 1000) 2 asin(sqrt(q))
+ *                     1 time_h       (double)index * (dt_s / (3600 substeps)): hours since the track's first sample
+ *                     2 v            intensity (m/s)
+ *                     3 speed        forward speed (m/s)
+ *                     4 heading_deg  as above
+ *                     5 side_km      +distance when the site is to the right of the motion, -distance to the left, 0.0 when
+ *                                    undefined.  With (e, nn) the centre -> site direction of the wind footprint
+ *                                    (e = cos phis sin dlam, nn = cos phic sin phis - sin phic cos phis cos dlam) and
+ *                                    cross = ue nn - un e: right when cross < 0, left when cross > 0, undefined when cross == 0
+ *                                    (the site on the centre, a stationary segment)
+ *                     6 rmax_km      rm
+ *   counts          [n_site][n_group][n_band][n_bin] (int32): storms s in [group_off[g], group_off[g + 1]) with distance_km <=
+ *                   band_km[band] and v >= thresholds[bin].  The band test is made on the very double written to plane 0, so the
+ *                   counts are an exact function of planes 0 and 2.
+ * Arguments: dt_s finite and > 0; substeps in [1, 64]; rmax_const_km finite and >= 0, and 0 when rmax_km is given; 1 <= n_band <= 8
+ * bands, finite, > 0, strictly ascending and at most 5000 km; thresholds finite and strictly ascending; n_band * (n_bin + 1) <= 64;
+ * 1 <= n_t <= 2^20.  Every message begins with "tcr_approach:".
+ * One lane owns a (site, storm), its records arrive in record order and culling never removes an included record, so the argmin
+ * and its tie rule, and with them every output, are bit-identical from run to run, whatever the launch shape, the site order, the
+ * storm order or the chunking.  _dev: planes, rmax_km, sites, counts and the planes `planes` points to are device memory,
+ * asynchronous on `stream`; band_km, thresholds, group_off and the pointer array are host memory in both entry points.  The workspace
+ * is the context's ninth: calls of tcr_approach_* on one context must be ordered, but one may be in flight next to a call of any
+ * other analysis on another stream. */
+#define TCR_APPROACH_PLANES 7
+typedef struct {
+    double dt_s;                 /* sample spacing (s) */
+    int32_t substeps;            /* records per sample interval, 1 .. 64 */
+    double rmax_const_km;        /* > 0: rm everywhere; 0: the rmax_km plane, or Willoughby et al. (2006) without one */
+} tcr_approach_params;
+int tcr_approach_dev(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const double *rmax_km, const tcr_approach_params *prm,
+                     int64_t n_site, const double *site_lon, const double *site_lat, int32_t n_band, const double *band_km,
+                     int32_t n_bin, const double *thresholds, int32_t *counts, double *const *planes, void *stream);
+int tcr_approach_host(tcr_ctx *ctx, const tcr_hazard_tracks *tracks, const double *rmax_km, const tcr_approach_params *prm,
+                      int64_t n_site, const double *site_lon, const double *site_lat, int32_t n_band, const double *band_km,
+                      int32_t n_bin, const double *thresholds, int32_t *counts, double *const *planes);
+/* (site, record) pairs the last tcr_approach_* call of this context evaluated after culling; waits for that call */
+int tcr_approach_pairs(tcr_ctx *ctx, int64_t *pairs);
+
 /* ---- row selection (return levels): the k-th largest value of every row of a per-storm plane ----------------------------- */
 /* replaces: nothing in the reference's code; the inverse of the return periods above.  With return_period = total_years /
  * count(peak >= v), the level of period T at a site is the k-th largest storm peak there, k the smallest integer with

@@ -17,6 +17,7 @@ FLAG_IS_TC, FLAG_ACCEPTED = 1, 2
 RAIN_TOTAL, RAIN_PEAK_RATE = 0, 1        # TCR_RAIN_*: tcr_rain_params.stat
 SELECT_LDS_KEYS, SELECT_MAX_RANKS = 8192, 64     # TCR_SELECT_*: keys of a row tcr_select_* selects in LDS, ranks of one call
 TAIL_MAX_K = 2048                 # TCR_TAIL_MAX_K: exceedances of a row tcr_tail_* fits
+APPROACH_PLANES = 7               # TCR_APPROACH_PLANES: the per-storm planes of tcr_approach_*
 ROWPACK_UNROLL = 8                # TCR_ROWPACK_UNROLL: a workgroup of tcr_rowpack_* takes 256 x this many columns of a row per turn
 STAGES = ('start', 'seed', 'select', 'order', 'gather', 'fourier', 'integrate', 'screen', 'select_tc', 'dense', 'emit', 'flags', 'stats', 'pack')
 STATIC_MODES = ('f64', 'f64_split', 'pack16', 'u8_f32', 'pack64')     # StaticMode (tcr_static_info)
@@ -46,6 +47,7 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_compound_dev', 'tcr_compound_host', 'tcr_compound_pairs', 'tcr_duration_dev', 'tcr_duration_host', 'tcr_duration_pairs',
            'tcr_accumulation_dev', 'tcr_accumulation_host', 'tcr_accumulation_pairs',
            'tcr_directional_dev', 'tcr_directional_host', 'tcr_directional_pairs',
+           'tcr_approach_dev', 'tcr_approach_host', 'tcr_approach_pairs',
            'tcr_select_dev', 'tcr_select_host', 'tcr_tail_dev', 'tcr_tail_host', 'tcr_rowpack_count_dev', 'tcr_rowpack_fill_dev', 'tcr_rowpack_host',
            'tcr_probe_rhs_f32_host', 'tcr_integrate_steps_host', 'tcr_integrate_steps_f32_host')
 TCR_COMM_ID_BYTES = 128
@@ -155,6 +157,11 @@ class RainParams(C.Structure):
     a[i] + b[i] U), sub-steps and the statistic (RAIN_TOTAL, RAIN_PEAK_RATE) of tcr_rainfall_*."""
     _fields_ = [('dt_s', C.c_double), ('r_out_km', C.c_double), ('v_lo_kt', C.c_double), ('v_hi_kt', C.c_double),
                 ('a', C.c_double * 4), ('b', C.c_double * 4), ('substeps', C.c_int32), ('stat', C.c_int32)]
+
+
+class ApproachParams(C.Structure):
+    """tcr_approach_params: sample spacing, sub-steps and constant rm (0: the plane, or modelled) of tcr_approach_*."""
+    _fields_ = [('dt_s', C.c_double), ('substeps', C.c_int32), ('rmax_const_km', C.c_double)]
 
 
 class TcrError(RuntimeError):
@@ -318,6 +325,10 @@ def lib():
                                       C.c_int32, C.c_double, C.c_int32, DP, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
     L.tcr_directional_host.argtypes = L.tcr_directional_dev.argtypes[:-1]
     L.tcr_directional_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    L.tcr_approach_dev.argtypes = [C.c_void_p, C.POINTER(HazardTracks), C.c_void_p, C.POINTER(ApproachParams), C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_int32, DP, C.c_int32, DP, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
+    L.tcr_approach_host.argtypes = L.tcr_approach_dev.argtypes[:-1]
+    L.tcr_approach_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     L.tcr_select_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_void_p,
                                  C.c_void_p, C.c_void_p]
     L.tcr_select_host.argtypes = L.tcr_select_dev.argtypes[:-1]

@@ -168,6 +168,7 @@ int tcr_tune_get(tcr_ctx *ctx, tcr_tune *t)
 #include "tcr_duration.hip"              // wind duration (hours at or above wind levels at sites: integer half-weights per level)
 #include "tcr_directional.hip"           // directional wind (peak footprint wind from each compass sector at sites: a max per sector)
 #include "tcr_accumulation.hip"          // rain accumulation windows (peak rain depth in any m consecutive samples at sites: a ring of running depths per lane)
+#include "tcr_approach.hip"              // closest approach (the nearest record of every storm to every site and what the storm was doing there: an argmin with a payload)
 #include "tcr_select.hip"                // row selection (the k-th largest of every row of a per-storm plane: return levels)
 #include "tcr_tail.hip"                  // row tail fit (a GPD fitted to the k largest of every row: return levels past the record)
 #include "tcr_rowpack.hip"               // row packing (the entries of every row of a per-storm plane at or above a floor, as CSR: event footprints)

@@ -189,9 +189,9 @@ struct Trace {
 struct Analyses {
     // site hazard (tcr_hazard.hip), wind footprint (tcr_windfield.hip), portfolio loss (tcr_loss.hip), rainfall
     // (tcr_rainfall.hip), compound hazard (tcr_compound.hip), wind duration (tcr_duration.hip), rain accumulation windows
-    // (tcr_accumulation.hip) and directional wind (tcr_directional.hip): a workspace each, so that one call of each may be in
-    // flight on streams of their own
-    ScanWs hz, wf, ls, rf, cp, du, ac, dr;
+    // (tcr_accumulation.hip), directional wind (tcr_directional.hip) and closest approach (tcr_approach.hip): a workspace each, so
+    // that one call of each may be in flight on streams of their own
+    ScanWs hz, wf, ls, rf, cp, du, ac, dr, ca;
     // landfall (tcr_landfall.hip): node coordinates (lon, then lat) and land bit plane of the uploaded grid
     DevArray<double> lf_xy;
     DevArray<uint32_t> lf_bits;

@@ -13,7 +13,10 @@ an optional [n_site][n_trk] plane.  Each binds its arguments once (its ``_bind``
 engine=None, device=0)`` -> (dict with ``planes`` = {row: plane} for the rows in want, Flavour), which its public function, its
 command line and ``stacked_return_levels`` call, any number of times: every call makes its own parameter struct and keeps it, the
 thresholds and the row arrays alive until the library returns.  ``wanted_rows``, ``stacked_scan``, ``stacked_planes``,
-``attach_planes`` and ``stacked_return_levels`` are what they share."""
+``attach_planes`` and ``stacked_return_levels`` are what they share.
+
+A ninth analysis, the closest approach, also counts per row (a distance band), but its per-storm planes are not its rows: they are
+the named parameters of the passage.  ``named_scan`` is ``stacked_scan`` for that shape."""
 import collections
 import ctypes as C
 
@@ -215,6 +218,28 @@ def stacked_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, n
     n_site, n_grp = int(res['counts'].shape[0]), int(res['counts'].shape[1])
     res['counts'] = res['counts'].reshape(n_site, n_grp, n_row, n_bin)
     res['planes'] = {i: res.pop('%s%d' % (prefix, i)) for i in want}
+    return res
+
+
+def named_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, n_row, names, want, engine, device, make_args):
+    """site_scan for an entry point whose per-storm planes are not its rows (closest approach: the rows are distance bands, the
+    planes the passage's parameters): ``counts`` comes back as [n_site][n_groups][n_row][n_bin] and ``planes`` as
+    {name: [n_site][n_trk] plane} for the names in want (a subset of names, the entry point's fixed list of planes).
+    make_args(ScanArgs, arr): arr is the entry point's array of len(names) plane pointers (NULL for a plane not wanted), or None
+    when want is empty."""
+    n_bin = int(thr.shape[0])
+    want = [k for k in names if k in want]
+
+    def args(a):
+        arr = (C.c_void_p * len(names))()
+        for k, p in zip(want, a.outputs):
+            arr[names.index(k)] = p
+        return make_args(a._replace(outputs=[]), arr if want else None)
+    res = site_scan(entry, planes, fl, groups, n_groups, site_lon, site_lat, thr, False, engine, device, args,
+                    more_outputs=[(k, 'pair') for k in want], count_cells=n_row * n_bin)
+    n_site, n_grp = int(res['counts'].shape[0]), int(res['counts'].shape[1])
+    res['counts'] = res['counts'].reshape(n_site, n_grp, n_row, n_bin)
+    res['planes'] = {k: res.pop(k) for k in want}
     return res
 
 
