@@ -8,7 +8,8 @@ rk.py / common.py / ivp.py) and compared; nothing is integrated on the reference
   3  K[0] of the first record and every K[6] against the single-point probe at their exactly known inputs, bit for bit;
   4  K[1..5] against the reference right-hand side at the restated stage inputs, in the units of tests/test_rhs_f32.py part C;
   5  err < 1, the next h from the error norm, the first h from select_initial_step;
-  6  dense output, emission, NaN padding and accept test 1, bit for bit;
+  6  dense output, the emitted lon, lat, v, m, their NaN padding and accept test 1, bit for bit (of vmax and envw only the NaN padding
+     is looked at here: their values and accept test 2 are pinned by tests/test_emit.py);
   7  parking / restoring and a short record change nothing.
 The CPU tests prove the restatement (its float64 mode walks scipy.integrate.RK45's steps) and the checker (synthetic float32
 records pass; planted defects of 2^-14 fail) before a GPU sees either.
@@ -317,7 +318,8 @@ def expected_n_valid(b, i, grid):
 
 
 def check_dense(b, prm, tab=None, planes=None):
-    """6.  Bit for bit.  Returns the number of rows compared."""
+    """6.  lon, lat, v, m and is_tc bit for bit.  `planes` are only checked for NaN past n_valid — what vmax and envw hold before
+    that is tests/test_emit.py's business.  Returns the number of rows compared."""
     grid = rk.Grid(prm.total_time, prm.n_steps)
     R, rows_seen = b['R'], 0
     for i in range(len(b['status'])):
