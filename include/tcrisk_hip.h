@@ -1088,6 +1088,54 @@ int tcr_rowpack_fill_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64
 int tcr_rowpack_host(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, double min_value,
                      int64_t *row_ptr, int64_t capacity, int32_t *col, double *val);
 
+/* ---- joint hazard (co-exceedance between sites): one bit per (row, level, unit), and popcounts of ANDed bit rows -------------- */
+/* replaces: nothing in the reference's code.  Every site analysis above treats sites one at a time; this says whether two sites
+ * are hit by the same storm, or in the same year: joint[i][j] = the number of units (storms, or years) that reached a level at
+ * site i and at site j.  A site analysis writes its per-storm plane for a block of sites; the plane becomes one bit per (site,
+ * level, unit) while it is on the device, and the counts are popcounts of ANDed bit rows.  Every result is an integer.
+ *   plane           [n_row][row_stride] fp64, of which the first n_col values of a row are the row (tcr_select's rules).
+ *   level           [n_row][n_level] fp64, not NaN, per row (an absolute threshold is the same value in every row).
+ *   reaches         column c of row r reaches level l iff plane[r][c] >= level[r][l] as an IEEE comparison, the comparison of
+ *                   `counts` and of tcr_rowpack: a NaN of either sign never reaches, -0.0 >= 0.0 reaches, +inf as a level admits
+ *                   only +inf, -inf admits every value that is not NaN.
+ *   unit            unit_of == NULL: unit = column, one bit per storm, n_unit = n_col.  Otherwise unit_of [n_col] int32 in
+ *                   [0, n_unit), and bit u is set iff ANY column with unit_of[c] == u reaches the level ("both sites exceeded in
+ *                   the same season").  The mapping is arbitrary: it need not be sorted, and units may be empty.
+ *   bits            bits[l * level_stride + r * n_word + (u >> 6)] is a uint64 whose bit u & 63 is unit u, n_word =
+ *                   ceil(n_unit / 64).  Bits at or past n_unit in the last word of a row are zero.  level_stride is in words and
+ *                   >= n_row * n_word; it may be that of a larger table of n_row_total rows (level_stride >= n_row_total * n_word)
+ *                   into which a block of rows is packed by passing bits + first_row * n_word.
+ *   n_set           [n_level][n_set_stride] int32 (n_set_stride >= n_row), or NULL: n_set[l][r] = the popcount of row r at level l.
+ *   counts          tcr_joint_cross_dev: [n_level][n_a][n_b] int32, counts[l][i][j] = sum over w of popcount(a[l][i][w] &
+ *                   b[l][j][w]).  a_bits == b_bits is allowed (the full square is computed; its diagonal is n_set).
+ * The results are functions of the inputs alone: a word is a ballot or an OR of bits, a count a sum of integers.  No
+ * floating-point atomics and no global atomics are used.
+ * Limits: 1 <= n_level <= TCR_JOINT_MAX_LEVELS; n_col in [1, 2^31 - 1]; with unit_of, 1 <= n_unit <= TCR_JOINT_MAX_MAPPED_UNITS,
+ * without it n_unit == n_col.  tcr_joint_cross_dev: n_a <= 65535 x 64, n_b < 2^30, n_word <= 2^25.  Every message begins with
+ * "tcr_joint:" and nothing is launched after one.  n_row == 0 (n_a == 0 or n_b == 0) does nothing and returns 0.
+ *   tcr_joint_pack_dev    plane, level, unit_of, bits and n_set are device memory, asynchronous on `stream`.  It cannot look at
+ *                         the entries of level or unit_of: a NaN level is reached by nothing, and a column whose unit_of is not
+ *                         in [0, n_unit) sets no bit.  Without unit_of one workgroup per row makes the ballots of 64 adjacent
+ *                         columns the words, all levels on one load of the plane; with it the hits of a row are ORed into an
+ *                         image of the row in LDS, for as many levels at a time as 4096 words hold.
+ *   tcr_joint_cross_dev   a_bits, b_bits and counts are device memory.  One workgroup per 64 x 64 tile of counts[l] walks the
+ *                         words in chunks of TCR_JOINT_KW.
+ *   tcr_joint_host        everything in host memory: uploads the plane, packs it and crosses the table with itself, counts
+ *                         [n_level][n_row][n_row], n_set [n_level][n_row] or NULL.  It also checks the entries of level (NaN) and
+ *                         of unit_of (range).  For the ABI-only user and for tests: when plane, table and counts together exceed
+ *                         2^32 bytes it fails with a message ("too large for tcr_joint_host") before anything is allocated.
+ * No workspace: calls on one context need no ordering. */
+#define TCR_JOINT_MAX_LEVELS 16
+#define TCR_JOINT_MAX_MAPPED_UNITS 262144      /* 2^18: one level of a mapped row is 4096 words of LDS */
+#define TCR_JOINT_KW 32               /* words of a bit row a workgroup of tcr_joint_cross_dev stages per chunk: 2 x 16.5 KB of LDS */
+int tcr_joint_pack_dev(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, const double *level,
+                       int32_t n_level, const int32_t *unit_of, int64_t n_unit, uint64_t *bits, int64_t level_stride, int32_t *n_set,
+                       int64_t n_set_stride, void *stream);
+int tcr_joint_cross_dev(tcr_ctx *ctx, const uint64_t *a_bits, int64_t n_a, int64_t a_level_stride, const uint64_t *b_bits, int64_t n_b,
+                        int64_t b_level_stride, int64_t n_word, int32_t n_level, int32_t *counts, void *stream);
+int tcr_joint_host(tcr_ctx *ctx, const double *plane, int64_t n_row, int64_t n_col, int64_t row_stride, const double *level,
+                   int32_t n_level, const int32_t *unit_of, int64_t n_unit, int32_t *counts, int32_t *n_set);
+
 #ifdef __cplusplus
 }
 #endif

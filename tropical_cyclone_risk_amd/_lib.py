@@ -19,6 +19,7 @@ SELECT_LDS_KEYS, SELECT_MAX_RANKS = 8192, 64     # TCR_SELECT_*: keys of a row t
 TAIL_MAX_K = 2048                 # TCR_TAIL_MAX_K: exceedances of a row tcr_tail_* fits
 APPROACH_PLANES = 7               # TCR_APPROACH_PLANES: the per-storm planes of tcr_approach_*
 ROWPACK_UNROLL = 8                # TCR_ROWPACK_UNROLL: a workgroup of tcr_rowpack_* takes 256 x this many columns of a row per turn
+JOINT_MAX_LEVELS, JOINT_MAX_MAPPED_UNITS, JOINT_KW = 16, 2 ** 18, 32      # TCR_JOINT_*: levels of one bit table, units behind unit_of, words per chunk of tcr_joint_cross_dev
 STAGES = ('start', 'seed', 'select', 'order', 'gather', 'fourier', 'integrate', 'screen', 'select_tc', 'dense', 'emit', 'flags', 'stats', 'pack')
 STATIC_MODES = ('f64', 'f64_split', 'pack16', 'u8_f32', 'pack64')     # StaticMode (tcr_static_info)
 N_STATS = 10        # TCR_N_STATS: words of a tcr_stats_dev / tcr_round.stats counter block
@@ -49,6 +50,7 @@ EXPORTS = ('tcr_abi_version', 'tcr_ctx_create', 'tcr_ctx_destroy', 'tcr_last_err
            'tcr_directional_dev', 'tcr_directional_host', 'tcr_directional_pairs',
            'tcr_approach_dev', 'tcr_approach_host', 'tcr_approach_pairs',
            'tcr_select_dev', 'tcr_select_host', 'tcr_tail_dev', 'tcr_tail_host', 'tcr_rowpack_count_dev', 'tcr_rowpack_fill_dev', 'tcr_rowpack_host',
+           'tcr_joint_pack_dev', 'tcr_joint_cross_dev', 'tcr_joint_host',
            'tcr_probe_rhs_f32_host', 'tcr_integrate_steps_host', 'tcr_integrate_steps_f32_host')
 TCR_COMM_ID_BYTES = 128
 
@@ -338,6 +340,12 @@ def lib():
     L.tcr_rowpack_fill_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
     L.tcr_rowpack_host.argtypes = L.tcr_rowpack_fill_dev.argtypes[:-1]
+    L.tcr_joint_pack_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    L.tcr_joint_cross_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                      C.c_void_p, C.c_void_p]
+    L.tcr_joint_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.c_void_p]
     if L.tcr_abi_version() != TCR_ABI_VERSION:
         raise TcrError('libtcrisk_hip.so ABI version %d != binding version %d'
                        % (L.tcr_abi_version(), TCR_ABI_VERSION))

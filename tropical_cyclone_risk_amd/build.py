@@ -15,7 +15,7 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, 'csrc')
 OUT = os.path.join(PKG, 'libtcrisk_hip.so')
-SOURCES = ['tcr_abi.hip', 'tcr_host.h', 'tcr_ctx.h', 'tcr_stage.hip', 'tcr_integrate.hip', 'tcr_preprocess.hip', 'tcr_round.hip', 'tcr_kernels.hip', 'tcr_seed.hip', 'tcr_compact.hip', 'tcr_prep.hip', 'tcr_thermo.hip', 'tcr_comm.hip', 'tcr_hazard.hip', 'tcr_landfall.hip', 'tcr_climatology.hip', 'tcr_windfield.hip', 'tcr_loss.hip', 'tcr_rainfall.hip', 'tcr_compound.hip', 'tcr_duration.hip', 'tcr_directional.hip', 'tcr_accumulation.hip', 'tcr_approach.hip', 'tcr_select.hip', 'tcr_tail.hip', 'tcr_rowpack.hip', 'tcr_sitescan.h', 'tcr_device.h', 'tcr_experiments.h',
+SOURCES = ['tcr_abi.hip', 'tcr_host.h', 'tcr_ctx.h', 'tcr_stage.hip', 'tcr_integrate.hip', 'tcr_preprocess.hip', 'tcr_round.hip', 'tcr_kernels.hip', 'tcr_seed.hip', 'tcr_compact.hip', 'tcr_prep.hip', 'tcr_thermo.hip', 'tcr_comm.hip', 'tcr_hazard.hip', 'tcr_landfall.hip', 'tcr_climatology.hip', 'tcr_windfield.hip', 'tcr_loss.hip', 'tcr_rainfall.hip', 'tcr_compound.hip', 'tcr_duration.hip', 'tcr_directional.hip', 'tcr_accumulation.hip', 'tcr_approach.hip', 'tcr_select.hip', 'tcr_tail.hip', 'tcr_rowpack.hip', 'tcr_joint.hip', 'tcr_sitescan.h', 'tcr_device.h', 'tcr_experiments.h',
            os.path.join('..', '..', 'include', 'tcrisk_hip.h')]
 # -disable-machine-licm: the kernels here are register-bound loops around libm-heavy bodies; hoisting the bodies' constant
 # materialisations out of the loops costs k_emit 40 VGPRs + spills (0.36 instead of 0.15 ms) and k_integrate 70 AGPRs.

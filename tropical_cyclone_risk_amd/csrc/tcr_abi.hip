@@ -172,3 +172,4 @@ int tcr_tune_get(tcr_ctx *ctx, tcr_tune *t)
 #include "tcr_select.hip"                // row selection (the k-th largest of every row of a per-storm plane: return levels)
 #include "tcr_tail.hip"                  // row tail fit (a GPD fitted to the k largest of every row: return levels past the record)
 #include "tcr_rowpack.hip"               // row packing (the entries of every row of a per-storm plane at or above a floor, as CSR: event footprints)
+#include "tcr_joint.hip"                 // joint hazard (one bit per (site, level, unit) of a per-storm plane, popcounts of ANDed bit rows: co-exceedance between sites)
